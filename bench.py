@@ -11,9 +11,12 @@ filters = a few GB, SURVEY §8 e) and each rank matches its own batch — weak s
 collective on the data path; one barrier + a MAX of the per-rank time brackets the timed
 region.
 
-Prints ONE JSON line (rank 0).  Extra keys: evals_per_s, roofline (HBM, algorithmic bytes of
-the fused match kernel per launch ÷ its HIP-event duration), cpu_baseline (the oracle's C++
-restatement of emqx_trie's compact DFS, timed on host cores on a bounded topic sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the
+headline (value, ms_per_step, evals_per_s).  ``--full`` adds what takes runs of its own:
+roofline (HBM, algorithmic bytes of the fused match kernel per launch ÷ its HIP-event duration,
+from synchronous calls), host_api (the host-buffer entry points), cpu_baseline (the oracle's
+C++ restatement of emqx_trie's compact DFS, timed on host cores on a bounded topic sample) and
+its parity check.  ``--dump-outputs DIR`` writes the last timed step's CSR (dump_outputs).
 """
 
 from __future__ import annotations
@@ -75,6 +78,15 @@ def main():
                     help="timed steps (default: 1000 for the batch-match workloads A / B / C1, so the timed "
                          "region lasts ~0.1-1 s rather than ~10 ms; 20 for the others)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="batch-match workloads (A / B / D): beside the headline figure, also the kernel / call "
+                         "times and roofline from synchronous calls, the host-buffer (PCIe-inclusive) rates, and "
+                         "the CPU baseline with its ID-for-ID parity check; without it the run sets up, warms "
+                         "up, times the steps and prints the result line (the other workloads and --sharded "
+                         "are chosen explicitly and run whole either way)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="batch-match workloads (A / B / D): after the timed steps, write the CSR the last timed "
+                         "step produced to DIR as .npy files (see dump_outputs)")
     ap.add_argument("--n-filters", type=int, default=10_000_000)
     ap.add_argument("--batch", type=int, default=None,
                     help="topics per batch (default 1M; --workload D: D_BATCH)")
@@ -84,8 +96,10 @@ def main():
                          "ID-for-ID with the oracle (default: the whole 1M batch; --workload D: 40k, ~15 s)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (default 0: every host core this process may use)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-api", action="store_true", help="skip the host-buffer (PCIe-inclusive) rates")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="skip the CPU baseline (batch-match workloads run it only with --full)")
+    ap.add_argument("--no-host-api", action="store_true",
+                    help="with --full: skip the host-buffer (PCIe-inclusive) rates")
     ap.add_argument("--cache", type=str, default=None,
                     help="npz path: reuse the generated workload across runs (profiling passes)")
     ap.add_argument("--ab", type=str, default=None,
@@ -172,6 +186,10 @@ def main():
         args.cpu_sample = {"D": 40_000}.get(args.workload, 1_000_000)
     if args.steps is None:
         args.steps = 1000 if args.workload in ("A", "B") and not args.sharded and not args.ab else 20
+    if args.dump_outputs and (args.workload not in ("A", "B", "D") or args.sharded or args.ab):
+        ap.error("--dump-outputs is for the batch-match workloads (A / B / D, not --sharded / --ab)")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     import torch
     import torch.distributed as dist
@@ -269,6 +287,7 @@ def main():
             cap = int(err.needed * 1.25) + 1024
             d_ids = torch.empty(cap, dtype=torch.int32, device=dev)
             nout = step()
+    evals = eng.stats()["last_evals"]  # of batch 0 (the last synchronous call)
     if args.ab:
         return ab_variants(eng, step, args, wl)
     # Timed steps are enqueued with emqx_match_batch_device_async, as a pipelined caller
@@ -321,15 +340,22 @@ def main():
                          f"totals {set(sm[:, 1].tolist())} vs {set(want_tot.tolist())}")
     if nouts[0] != nout:
         raise SystemExit(f"batch 0 total {nouts[0]} != {nout}")
-    # kernel / call times from synchronous calls (HIP events on the engine's stream)
+    if args.dump_outputs and args.steps:
+        # the last timed step's CSR, still in its stream's output buffers
+        last = args.steps - 1
+        d_off_l, d_ids_l = outs[last % len(streams)]
+        dump_outputs(args.dump_outputs, "" if world == 1 else f"rank{rank}_", d_off_l.cpu().numpy(),
+                     d_ids_l[: int(sm[last, 1])].cpu().numpy().view(np.uint32), wl.n_filters)
+    # --full: kernel / call times from synchronous calls (HIP events on the engine's stream)
     kern_ms, call_ms, order_ms = [], [], []
-    for _ in range(min(max(args.steps, 1), 10)):
+    for _ in range(min(max(args.steps, 1), 10) if args.full else 0):
         step()
         st = eng.stats()
         kern_ms.append(st["last_kernel_ms"])
         call_ms.append(st["last_match_ms"])
         order_ms.append(st["last_order_ms"])
-    evals = eng.stats()["last_evals"]
+    if args.full:
+        evals = eng.stats()["last_evals"]
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -347,15 +373,17 @@ def main():
     done = np.sort([ev0.elapsed_time(e) for e in evs]) if args.steps else np.zeros(0)
     gaps = np.diff(np.concatenate([[0.0], done]))
 
-    # roofline of the fused match kernel (rank 0's launch), live kernel time (HIP events)
-    offs = wl.topics[1].astype(np.int64)
-    tbytes = int(offs[-1] - offs[0])
-    levels = int(np.count_nonzero(wl.topics[0][: tbytes] == ord("/"))) + n
-    kms = float(np.mean(kern_ms)) if kern_ms else float("nan")
-    traffic, traffic_src = args.traffic_bytes, "--traffic-bytes"
-    if traffic is None:
-        traffic, traffic_src = measured_traffic(n, args)
-    roofline = match_roofline(n, kms, args, tbytes, levels, evals, nout, traffic, traffic_src)
+    # --full: roofline of the fused match kernel (rank 0's launch), live kernel time (HIP events)
+    roofline = None
+    if args.full:
+        offs = wl.topics[1].astype(np.int64)
+        tbytes = int(offs[-1] - offs[0])
+        levels = int(np.count_nonzero(wl.topics[0][: tbytes] == ord("/"))) + n
+        kms = float(np.mean(kern_ms)) if kern_ms else float("nan")
+        traffic, traffic_src = args.traffic_bytes, "--traffic-bytes"
+        if traffic is None:
+            traffic, traffic_src = measured_traffic(n, args)
+        roofline = match_roofline(n, kms, args, tbytes, levels, evals, nout, traffic, traffic_src)
 
     result = {
         "metric": "published topics matched/sec (and match evals/sec) at 10M subs; % of HBM BW",
@@ -380,16 +408,16 @@ def main():
         "evals_per_s": round(evals_all * args.steps / elapsed, 1),
         "matches_per_topic": round(nout_all / (n * world), 3),
         "evals_per_topic": round(evals_all / (n * world), 3),
-        "call_ms_avg": round(float(np.mean(call_ms)), 4),
-        "order_ms_avg": round(float(np.mean(order_ms)), 4),
+        **({"call_ms_avg": round(float(np.mean(call_ms)), 4),
+            "order_ms_avg": round(float(np.mean(order_ms)), 4)} if args.full else {}),
         "step_completion_gap_ms": {"p50": round(float(np.median(gaps)), 4) if gaps.size else None,
                                    "max": round(float(np.max(gaps)), 4) if gaps.size else None},
         "host_enqueue_ms_per_step": round(1e3 * t_enq / max(args.steps, 1), 4),
         "step_gaps_ms": [round(float(g), 3) for g in gaps] if args.steps <= 64 else None,
-        "roofline": roofline,
+        **({"roofline": roofline} if args.full else {}),
     }
 
-    if world == 1 and not args.no_host_api:
+    if args.full and world == 1 and not args.no_host_api:
         result["host_api"] = host_api_rates(eng, wl, args, nout)
 
     if args.diag:
@@ -405,7 +433,7 @@ def main():
                                    "steps": round(d["steps"] / w, 2), "waves": d.get("waves", 0)}
         result["diag_per_topic"]["kernel_ms_diag_call"] = round(eng.stats()["last_kernel_ms"], 4)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the GPU CSR of the last synchronous call (the whole batch), compared ID-for-ID
         k = min(args.cpu_sample, n)
         off_g = d_off[: k + 1].cpu().numpy()
@@ -1906,6 +1934,41 @@ def update_cpu_baseline(wl, nb, k, args):
     return {"value": round(ops / t_total, 1), "unit": "updates/s", "cores": 1, "kind": "port",
             "sample": f"{r} rounds of {k} deletes + {k} inserts on the same {nb}-filter table (C++ restatement "
                       "of emqx_trie:insert/delete key maintenance, no mnesia transaction, one writer)"}
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(dirpath, prefix, off, ids, n_filters, seed=0):
+    """--dump-outputs: the CSR one match call returned (`off`: n + 1 offsets, `ids`: the matched
+    filter ids), written so that two builds can be compared array for array.  The order of one
+    topic's ids is not part of the API (they are compared as sets everywhere), so each topic's
+    ids are written ascending.  Files (float64 unless noted; every value is an integer that the
+    format holds exactly):
+
+      topics.npy  indices of the topics written, ascending: all of them when the output fits
+                  DUMP_BUDGET_BYTES, else the longest prefix of a fixed seeded permutation of
+                  the batch that does
+      counts.npy  matches of each of those topics
+      ids.npy     their ids, topic after topic (float32 when every filter id is below 2^24)
+    """
+    off = np.asarray(off).astype(np.int64)
+    n = len(off) - 1
+    cnt = np.diff(off)
+    id_dtype = np.float32 if n_filters <= (1 << 24) else np.float64
+    perm = np.random.default_rng(seed).permutation(n)
+    cost = np.cumsum(16 + np.dtype(id_dtype).itemsize * cnt[perm])
+    sel = np.sort(perm[: int(np.searchsorted(cost, DUMP_BUDGET_BYTES, side="right"))])
+    c = cnt[sel]
+    first = np.cumsum(c) - c  # where each selected topic starts in the written ids
+    src = np.repeat(off[sel] - first, c) + np.arange(int(c.sum()), dtype=np.int64)
+    tt = np.repeat(np.arange(len(sel), dtype=np.int64), c)
+    out = np.sort((tt << 32) | ids[src].astype(np.int64)) & 0xFFFFFFFF
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, prefix + "topics.npy"), sel.astype(np.float64))
+    np.save(os.path.join(dirpath, prefix + "counts.npy"), c.astype(np.float64))
+    np.save(os.path.join(dirpath, prefix + "ids.npy"), out.astype(id_dtype))
+    log(f"dumped {len(sel)} of {n} topics, {len(out)} ids to {dirpath}")
 
 
 def set_walk_order(eng, args):

@@ -11,7 +11,7 @@ if [ "${2:-}" = "--tests" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 1; }
   tail -2 $O/pytest_gpu.log
 fi
-timeout -k 10 400 python -u bench.py --workload D --cache /tmp/wlD > $O/benchD.json 2> $O/benchD.err || { tail -20 $O/benchD.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --workload D --cache /tmp/wlD > $O/benchD.json 2> $O/benchD.err || { tail -20 $O/benchD.err; exit 1; }
 cat $O/benchD.json
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$O/prof" -o run -- python3 "$ROOT/bench.py" --workload D --cache /tmp/wlD --no-cpu-baseline --streams 1 > "$ROOT/$O/prof_bench.json" 2> "$ROOT/$O/prof_bench.err" || { tail -20 "$ROOT/$O/prof_bench.err"; exit 1; }

@@ -4,7 +4,8 @@
 #
 #   bash tools/gpu.sh tests  OUT [pytest args...]         -m gpu tests -> OUT/pytest.log
 #   bash tools/gpu.sh smoke  OUT                          __graft_entry__.smoke() -> OUT/smoke.log
-#   bash tools/gpu.sh bench  OUT NAME [bench.py args...]  one bench line -> OUT/NAME.json (+ .err)
+#   bash tools/gpu.sh bench  OUT NAME [bench.py args...]  one bench line -> OUT/NAME.json (+ .err);
+#                                                         pass --full for its roofline and parity
 #   bash tools/gpu.sh prof   OUT NAME [bench.py args...]  rocprofv3 --kernel-trace --stats of the bench
 #                                                         -> OUT/NAME_prof/, top kernels printed
 #   bash tools/gpu.sh pmc    OUT NAME REGEX [bench.py args...]

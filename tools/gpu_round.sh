@@ -14,7 +14,7 @@ echo "== smoke"; date
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { echo smoke failed; tail -20 "$OUT/smoke.log"; exit 1; }
 tail -2 "$OUT/smoke.log"
 echo "== bench"; date
-timeout -k 10 600 python -u bench.py --cache /tmp/wlB > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo bench failed; tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 600 python -u bench.py --full --cache /tmp/wlB > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo bench failed; tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 echo "== rocprofv3 kernel stats"; date
 cd /tmp

@@ -13,7 +13,7 @@ i=0
 for setting in "$@"; do
   i=$((i+1))
   cd /tmp
-  env $setting timeout -k 10 120 python3 "$ROOT/bench.py" $ARGS > "$ROOT/$OUT/s$i.bench.json" 2> "$ROOT/$OUT/s$i.bench.err"
+  env $setting timeout -k 10 120 python3 "$ROOT/bench.py" --full $ARGS > "$ROOT/$OUT/s$i.bench.json" 2> "$ROOT/$OUT/s$i.bench.err"
   rc=$?; [ $rc -eq 0 ] || { cd "$ROOT"; echo "setting $i bench rc=$rc"; exit $rc; }
   for grp in "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum GRBM_GUI_ACTIVE"; do
     export $setting
