@@ -66,6 +66,13 @@ RETAIN_EXPORTS = (
     "emqx_retain_match_batch", "emqx_retain_match_batch_device", "emqx_retain_stats_get",
     "emqx_retain_match_spec_batch", "emqx_retain_set_tuning",
 )
+# Every symbol include/emqx_authz.h declares (batched authorization check).
+AUTHZ_EXPORTS = (
+    "emqx_authz_create", "emqx_authz_destroy", "emqx_authz_list_set", "emqx_authz_source_clear",
+    "emqx_authz_clients_set", "emqx_authz_clients_drop", "emqx_authz_commit", "emqx_authz_check_batch",
+    "emqx_authz_check_batch_device", "emqx_authz_check_batch_device_async", "emqx_authz_check_host",
+    "emqx_authz_set_tuning", "emqx_authz_stats_get",
+)
 
 NO_GROUP = 0xFFFFFFFF
 SHARD_NONE = 0xFFFFFFFF
@@ -118,6 +125,35 @@ class RetainStats(ctypes.Structure):
         ("last_spill_full", ctypes.c_uint64),
         ("last_shares", ctypes.c_uint64),
         ("queue_aborts", ctypes.c_uint64),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class AuthzRule(ctypes.Structure):
+    """struct emqx_authz_rule (include/emqx_authz.h)."""
+    _fields_ = [("permission", ctypes.c_uint8), ("action", ctypes.c_uint8), ("who_op", ctypes.c_uint8),
+                ("eq_topics", ctypes.c_uint8), ("n_who", ctypes.c_uint32), ("first_topic", ctypes.c_uint32),
+                ("n_topics", ctypes.c_uint32), ("tag", ctypes.c_uint32)]
+
+
+class AuthzWho(ctypes.Structure):
+    """struct emqx_authz_who (include/emqx_authz.h)."""
+    _fields_ = [("kind", ctypes.c_uint32), ("operand", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
+class AuthzStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("n_sources", ctypes.c_uint64), ("n_lists", ctypes.c_uint64), ("n_rules", ctypes.c_uint64),
+        ("n_entries", ctypes.c_uint64), ("n_clients", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64),
+        ("epoch", ctypes.c_uint64), ("last_evals", ctypes.c_uint64), ("last_group", ctypes.c_uint64),
+        ("last_build_ms", ctypes.c_double), ("last_check_ms", ctypes.c_double),
     ]
 
     def __init__(self, *a, **kw):
@@ -245,6 +281,19 @@ def lib():
         "emqx_retain_match_batch_device": (i32, [vp, vp, vp, u64, ctypes.c_int64, vp, vp, u64,
                                                  ctypes.POINTER(u64), vp]),
         "emqx_retain_stats_get": (i32, [vp, ctypes.POINTER(RetainStats)]),
+        "emqx_authz_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_authz_destroy": (i32, [vp]),
+        "emqx_authz_list_set": (i32, [vp, u32, u32, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64]),
+        "emqx_authz_source_clear": (i32, [vp, u32]),
+        "emqx_authz_clients_set": (i32, [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "emqx_authz_clients_drop": (i32, [vp, vp, u64]),
+        "emqx_authz_commit": (i32, [vp]),
+        "emqx_authz_check_batch": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
+        "emqx_authz_check_batch_device": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "emqx_authz_check_batch_device_async": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "emqx_authz_check_host": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
+        "emqx_authz_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_authz_stats_get": (i32, [vp, ctypes.POINTER(AuthzStats)]),
         "emqx_commit_stats": (i32, [vp, vp, u32]),
         "emqx_shard_owner": (i32, [vp, vp, u64, u32, u32, i32, vp]),
         "emqx_shard_owner_device": (i32, [vp, vp, u64, u32, u32, vp, vp]),

@@ -20,7 +20,8 @@
  *   emqx_trie:empty/0                        apps/emqx/src/emqx_trie.erl:164-171
  *       -> emqx_stats(...).n_filters == 0
  *   emqx_topic:match/2                       apps/emqx/src/emqx_topic.erl:65-87
- *       -> emqx_topic_match (CPU; per-pair callers such as authz stay on the CPU)
+ *       -> emqx_topic_match (CPU; binary arguments, with the '$' rule.  The authz check
+ *          calls match/2 on word lists, without that rule: emqx_authz.h)
  *
  * Conventions: plain C, no exceptions cross the ABI, every entry point returns an int
  * status (EMQX_OK = 0, negative = error) unless documented otherwise.  Topic/filter
