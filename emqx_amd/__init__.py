@@ -6,6 +6,8 @@ Modules mirror the reference's Erlang modules on the hot path:
   :mod:`emqx_amd.router`  emqx_router  (add/delete/match_routes/lookup_routes)
   :mod:`emqx_amd.engine`  the C-ABI engine handle (batched, device-resident matching)
   :mod:`emqx_amd.workloads` synthetic subscription tables / topic streams (BASELINE configs)
+  :mod:`emqx_amd.deliver` emqx_session ignore_local/3 + enrich_subopts/3 (No Local, granted QoS, RAP, subid
+                          per delivery behind the fan-out)
   :mod:`emqx_amd.dist`    multi-GPU: replicated tables + data-parallel topic split,
                           filter-sharded tables with broadcast + gather
 """
@@ -13,3 +15,4 @@ Modules mirror the reference's Erlang modules on the hot path:
 __version__ = "0.1.0"
 
 from ._lib import EngineError, MODE_ROUTES, MODE_TRIE, MODE_TRIE_WILDCARD  # noqa: F401
+from .deliver import SubOpts  # noqa: F401,E402  (delivery options behind the fan-out)

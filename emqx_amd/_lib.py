@@ -73,6 +73,13 @@ AUTHZ_EXPORTS = (
     "emqx_authz_check_batch_device", "emqx_authz_check_batch_device_async", "emqx_authz_check_host",
     "emqx_authz_set_tuning", "emqx_authz_stats_get",
 )
+# Every symbol include/emqx_deliver.h declares (delivery options behind the fan-out).
+DELIVER_EXPORTS = (
+    "emqx_subopts_create", "emqx_subopts_destroy", "emqx_subopts_set", "emqx_subopts_remove",
+    "emqx_subopts_drop_subscribers", "emqx_subopts_commit", "emqx_deliver_enrich_batch",
+    "emqx_deliver_enrich_batch_device", "emqx_deliver_enrich_batch_device_async", "emqx_deliver_enrich_host",
+    "emqx_subopts_set_tuning", "emqx_subopts_stats_get",
+)
 
 NO_GROUP = 0xFFFFFFFF
 SHARD_NONE = 0xFFFFFFFF
@@ -154,6 +161,34 @@ class AuthzStats(ctypes.Structure):
         ("n_entries", ctypes.c_uint64), ("n_clients", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64),
         ("epoch", ctypes.c_uint64), ("last_evals", ctypes.c_uint64), ("last_group", ctypes.c_uint64),
         ("last_build_ms", ctypes.c_double), ("last_check_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class DeliverBatch(ctypes.Structure):
+    """struct emqx_deliver_batch (include/emqx_deliver.h): the buffers of one enrich call."""
+    _fields_ = [
+        ("offsets", ctypes.c_void_p), ("subs", ctypes.c_void_p), ("filters", ctypes.c_void_p),
+        ("n", ctypes.c_uint64), ("cap_in", ctypes.c_uint64),
+        ("msg_qos", ctypes.c_void_p), ("msg_flags", ctypes.c_void_p), ("msg_from", ctypes.c_void_p),
+        ("out_opts", ctypes.c_void_p), ("out_subids", ctypes.c_void_p),
+        ("kept_offsets", ctypes.c_void_p), ("kept_subs", ctypes.c_void_p), ("kept_filters", ctypes.c_void_p),
+        ("kept_opts", ctypes.c_void_p), ("kept_subids", ctypes.c_void_p), ("cap_kept", ctypes.c_uint64),
+    ]
+
+
+class SubOptsStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("n_entries", ctypes.c_uint64), ("n_slots", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64),
+        ("epoch", ctypes.c_uint64), ("max_probe", ctypes.c_uint64),
+        ("last_build_ms", ctypes.c_double), ("last_call_ms", ctypes.c_double),
     ]
 
     def __init__(self, *a, **kw):
@@ -294,6 +329,18 @@ def lib():
         "emqx_authz_check_host": (i32, [vp, vp, vp, vp, vp, u64, vp, vp]),
         "emqx_authz_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_authz_stats_get": (i32, [vp, ctypes.POINTER(AuthzStats)]),
+        "emqx_subopts_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_subopts_destroy": (i32, [vp]),
+        "emqx_subopts_set": (i32, [vp, vp, vp, vp, vp, u64]),
+        "emqx_subopts_remove": (i32, [vp, vp, vp, u64]),
+        "emqx_subopts_drop_subscribers": (i32, [vp, vp, u64]),
+        "emqx_subopts_commit": (i32, [vp]),
+        "emqx_deliver_enrich_batch": (i32, [vp, ctypes.POINTER(DeliverBatch), ctypes.POINTER(u64), vp]),
+        "emqx_deliver_enrich_batch_device": (i32, [vp, ctypes.POINTER(DeliverBatch), ctypes.POINTER(u64), vp, vp]),
+        "emqx_deliver_enrich_batch_device_async": (i32, [vp, ctypes.POINTER(DeliverBatch), vp, vp]),
+        "emqx_deliver_enrich_host": (i32, [vp, ctypes.POINTER(DeliverBatch), ctypes.POINTER(u64), vp]),
+        "emqx_subopts_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_subopts_stats_get": (i32, [vp, ctypes.POINTER(SubOptsStats)]),
         "emqx_commit_stats": (i32, [vp, vp, u32]),
         "emqx_shard_owner": (i32, [vp, vp, u64, u32, u32, i32, vp]),
         "emqx_shard_owner_device": (i32, [vp, vp, u64, u32, u32, vp, vp]),

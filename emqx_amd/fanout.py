@@ -202,6 +202,10 @@ class Broker:
     def __init__(self, device: int = -1, node: object = "emqx@127.0.0.1", strategy="round_robin"):
         self.router = Router(device, node)
         self.subs = SubTable(device)
+        self.opts = None  # SubOpts (emqx_amd.deliver), created with the first recorded options
+        self._opts_dirty = False
+        self._device = device
+        self._msg_cap = 1 << 16  # delivery capacity of publish_messages, grown on EMQX_EOVERFLOW
         self.strategy = _strategy(strategy)
         self._sub_ids: Dict[Hashable, int] = {}
         self._subs_by_id: List[Hashable] = []
@@ -222,23 +226,32 @@ class Broker:
         return self._group_ids.setdefault(group, len(self._group_ids))
 
     # emqx_broker.erl:124-163 / emqx_shared_sub.erl:300-307
-    def subscribe(self, topic: bytes, sub, share=None) -> None:
+    def subscribe(self, topic: bytes, sub, share=None, subopts=None) -> None:
+        """``subopts`` (optional): the subscription's options as emqx_types:subopts(), a dict with
+        any of ``qos``, ``nl``, ``rap``, ``subid`` and the session's ``upgrade_qos``; recorded
+        under (filter, subscriber) as emqx_session:subscribe/4 does (a later one replaces an
+        earlier one, $share or not) and applied by :meth:`publish_messages`."""
         with self._lock:
-            if share is None:
-                s = self._plain.setdefault(topic, set())
-                if sub in s:
-                    return
-                s.add(sub)
-                self.router.add_route(topic)
-            else:
-                m = self._members.setdefault((topic, share), set())
-                if sub in m:
-                    return
-                m.add(sub)
-                self.router.add_route(topic, (share, self.router.node))
-            fid = self.router.engine.lookup(topic)
-            self.subs.add([fid], [self._sid(sub)], None if share is None else [self._gid(share)])
-            self._dirty = True
+            members = self._plain.setdefault(topic, set()) if share is None else \
+                self._members.setdefault((topic, share), set())
+            if sub not in members:
+                members.add(sub)
+                self.router.add_route(topic, None if share is None else (share, self.router.node))
+                fid = self.router.engine.lookup(topic)
+                self.subs.add([fid], [self._sid(sub)], None if share is None else [self._gid(share)])
+                self._dirty = True
+            if subopts is not None:
+                o = dict(subopts)
+                self._opts_table().set([self.router.engine.lookup(topic)], [self._sid(sub)], qos=o.get("qos", 0),
+                                       nl=o.get("nl", 0), rap=o.get("rap", 0), upgrade_qos=o.get("upgrade_qos", False),
+                                       subid=o.get("subid"))
+                self._opts_dirty = True
+
+    def _opts_table(self):
+        if self.opts is None:
+            from .deliver import SubOpts
+            self.opts = SubOpts(self._device)
+        return self.opts
 
     # emqx_broker.erl:169-195 / emqx_shared_sub.erl:309-314
     def unsubscribe(self, topic: bytes, sub, share=None) -> None:
@@ -250,6 +263,7 @@ class Broker:
                 s = self._plain.get(topic, set())
                 if sub not in s:
                     return
+                self._forget_opts(fid, sub)
                 s.discard(sub)
                 self.subs.remove([fid], [self._sid(sub)])
                 if not s:
@@ -258,17 +272,27 @@ class Broker:
                 m = self._members.get((topic, share), set())
                 if sub not in m:
                     return
+                self._forget_opts(fid, sub)
                 m.discard(sub)
                 self.subs.remove([fid], [self._sid(sub)], [self._gid(share)])
                 if not m:
                     self.router.delete_route(topic, (share, self.router.node))
             self._dirty = True
 
+    def _forget_opts(self, fid: int, sub) -> None:
+        # emqx_session:unsubscribe/4: maps:remove(TopicFilter, Subs)
+        if self.opts is not None:
+            self.opts.remove([fid], [self._sid(sub)])
+            self._opts_dirty = True
+
     def _sync(self):
         if self._dirty:
             self.router._sync()
             self.subs.commit()
             self._dirty = False
+        if self._opts_dirty:
+            self.opts.commit()
+            self._opts_dirty = False
 
     def publish_batch(self, topics: Sequence[bytes], keys: Optional[Sequence[int]] = None, strategy=None,
                       with_retry: bool = False):
@@ -294,6 +318,94 @@ class Broker:
 
     def publish(self, topic: bytes, key: int = 0):
         return self.publish_batch([topic], [key])[0]
+
+    def publish_messages(self, messages: Sequence[tuple], keys: Optional[Sequence[int]] = None, strategy=None,
+                         retained: bool = False):
+        """What goes on the wire for a batch of messages ``(topic, qos, retain, from_sub)``
+        (``from_sub``: the publishing client's subscriber handle or None): per message
+        ``[(filter, subscriber, shared, qos, retain, nl, subid)]`` with the No Local drops removed
+        (emqx_session:ignore_local/3) and the rest enriched (enrich_subopts/3).  Match, fan-out
+        and enrich run back to back on the device; neither CSR leaves HBM in between.  A
+        subscriber without recorded options gets the message unchanged (get_subopts: error -> []).
+        ``retained``: the messages come from the retainer's dispatch (headers.retained = true)."""
+        import torch
+        from .deliver import NO_SENDER, OUT_NL, OUT_RETAIN
+        self._sync()
+        opts = self._opts_table()
+        st = self.strategy if strategy is None else _strategy(strategy)
+        n = len(messages)
+        dev = torch.device("cuda", torch.cuda.current_device() if self._device < 0 else self._device)
+        buf, offs = pack([m[0] for m in messages])
+        frm = [NO_SENDER if m[3] is None else self._sub_ids.get(m[3], NO_SENDER) for m in messages]
+
+        def up(a, dtype):
+            return torch.from_numpy(np.array(a, dtype=dtype).view(
+                {np.uint64: np.int64, np.uint32: np.int32}.get(dtype, dtype))).to(dev)
+
+        d_buf, d_off = up(buf, np.uint8), up(offs, np.uint64)
+        d_qos = up([m[1] for m in messages] or [0], np.uint8)
+        d_flags = up([(1 if m[2] else 0) | (2 if retained else 0) for m in messages] or [0], np.uint8)
+        d_from = up(frm or [0], np.uint32)
+        d_keys = None if keys is None else up(list(keys) or [0], np.uint32)
+        d_moff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_doff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_koff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        engine = self.router.engine
+        cap = max(self._msg_cap, 1)
+        for _ in range(3):  # an EOVERFLOW names the capacity needed
+            try:
+                d_mids = torch.zeros(cap, dtype=torch.int32, device=dev)
+                n_match = engine.match_device(d_buf.data_ptr(), d_off.data_ptr(), n, d_moff.data_ptr(), d_mids.data_ptr(),
+                                              cap, mode=_lib.MODE_ROUTES)
+                break
+            except EngineError as e:
+                if e.code != _lib.EMQX_EOVERFLOW:
+                    raise
+                cap = e.needed + 1
+        else:
+            raise EngineError(_lib.EMQX_EOVERFLOW, "emqx_match_batch_device")
+        del n_match
+        for _ in range(3):
+            try:
+                d_subs = torch.zeros(cap, dtype=torch.int32, device=dev)
+                d_fils = torch.zeros(cap, dtype=torch.int32, device=dev)
+                total = self.subs.fanout_device(st, d_moff.data_ptr(), d_mids.data_ptr(), n,
+                                                None if d_keys is None else d_keys.data_ptr(), d_doff.data_ptr(),
+                                                d_subs.data_ptr(), d_fils.data_ptr(), cap)
+                break
+            except EngineError as e:
+                if e.code != _lib.EMQX_EOVERFLOW:
+                    raise
+                cap = e.needed + 1
+        else:
+            raise EngineError(_lib.EMQX_EOVERFLOW, "emqx_fanout_batch_device")
+        self._msg_cap = cap
+        m = max(total, 1)
+        d_out = torch.zeros(m, dtype=torch.uint8, device=dev)
+        d_ids = torch.zeros(m, dtype=torch.int32, device=dev)
+        k_subs, k_fils, k_ids = (torch.zeros(m, dtype=torch.int32, device=dev) for _ in range(3))
+        k_opts = torch.zeros(m, dtype=torch.uint8, device=dev)
+        summary = opts.enrich_device(opts.batch(
+            d_doff.data_ptr(), d_subs.data_ptr(), d_fils.data_ptr(), n, cap, d_qos.data_ptr(), d_flags.data_ptr(),
+            d_from.data_ptr(), d_out.data_ptr(), d_ids.data_ptr(), d_koff.data_ptr(), k_subs.data_ptr(),
+            k_fils.data_ptr(), k_opts.data_ptr(), k_ids.data_ptr(), m))
+        kept = summary["kept"]
+        off = d_koff.cpu().numpy()
+        subs = k_subs[:kept].cpu().numpy().view(np.uint32)
+        fils = k_fils[:kept].cpu().numpy().view(np.uint32)
+        bytes_ = k_opts[:kept].cpu().numpy()
+        ids = k_ids[:kept].cpu().numpy().view(np.uint32)
+        names = self.router._names
+        res = []
+        for i in range(n):
+            row = []
+            for j in range(int(off[i]), int(off[i + 1])):
+                f, o = int(fils[j]), int(bytes_[j])
+                row.append((names[f & ~(FANOUT_SHARED_BIT | FANOUT_RETRY_BIT)], self._subs_by_id[int(subs[j])],
+                            bool(f & FANOUT_SHARED_BIT), o & 3, bool(o & OUT_RETAIN), bool(o & OUT_NL),
+                            int(ids[j]) or None))
+            res.append(row)
+        return res
 
     def down(self, sub) -> None:
         """The subscriber's process went down (is_alive_sub/1 false); its subscriptions stay

@@ -1,0 +1,362 @@
+"""The enrich stage behind the fan-out on the device (include/emqx_deliver.h): every entry
+point against the restatement (tests/deliver_ref.py) and against the host evaluator, the tile
+and wave boundaries of the compaction, overflow and refusal, snapshot lifetime across a commit,
+and the match -> fan-out -> enrich chain on one stream."""
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import deliver_cases as C
+from tests import deliver_ref as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda:0"
+SENTINEL = 0x5A
+
+
+@pytest.fixture(scope="module")
+def D():
+    lib_path = os.path.join(ROOT, "emqx_amd", "_build", "libemqxmatch.so")
+    if not os.path.exists(lib_path):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "emqx_amd", "csrc"), "-j4"], check=True,
+                       capture_output=True)
+    import torch
+    assert torch.cuda.is_available()
+    torch.cuda.set_device(0)
+    from emqx_amd import deliver
+    return deliver
+
+
+def dev(a, dtype):
+    import torch
+    view = {np.uint64: np.int64, np.uint32: np.int32}.get(dtype, dtype)
+    a = np.array(a, dtype=dtype)  # a writable copy
+    if a.size == 0:
+        a = np.zeros(1, dtype=dtype)
+    return torch.from_numpy(a.view(view)).to(DEV)
+
+
+class DeviceBatch:
+    """A case's batch in device memory with sentinel-filled outputs."""
+
+    def __init__(self, D, case, compact, cap_kept=None, cap_in=None):
+        import torch
+        off, subs, fils, qos, flags, frm = case.batch
+        self.n, self.total = len(off) - 1, len(subs)
+        self.cap_in = self.total if cap_in is None else cap_in
+        self.cap_kept = self.total if cap_kept is None else cap_kept
+        self.ins = [dev(off, np.uint64), dev(subs, np.uint32), dev(fils, np.uint32), dev(qos, np.uint8),
+                    dev(flags, np.uint8), None if frm is None else dev(frm, np.uint32)]
+        m = max(self.total, 1)
+        def filled(k, dtype):  # every byte SENTINEL
+            return torch.full((k,), {torch.uint8: SENTINEL, torch.int32: 0x5A5A5A5A, torch.int64: 0x5A5A5A5A5A5A5A5A}[dtype],
+                              dtype=dtype, device=DEV)
+
+        self.opts, self.subids, self.koff = filled(m, torch.uint8), filled(m, torch.int32), filled(self.n + 1, torch.int64)
+        self.ksubs, self.kfils, self.kids = (filled(m, torch.int32) for _ in range(3))
+        self.kopts, self.summary = filled(m, torch.uint8), filled(8, torch.int64)
+        self.compact = compact
+        i = self.ins
+        self.args = D.SubOpts.batch(
+            i[0].data_ptr(), i[1].data_ptr(), i[2].data_ptr(), self.n, self.cap_in, i[3].data_ptr(), i[4].data_ptr(),
+            0 if i[5] is None else i[5].data_ptr(), self.opts.data_ptr(), self.subids.data_ptr(),
+            *((self.koff.data_ptr(), self.ksubs.data_ptr(), self.kfils.data_ptr(), self.kopts.data_ptr(),
+               self.kids.data_ptr(), self.cap_kept) if compact else ()))
+
+    def result(self, D, summary=None):
+        if summary is None:
+            summary = dict(zip(D.SUMMARY, self.summary.cpu().numpy().view(np.uint64).tolist()))
+        kept = None
+        if self.compact:
+            k = summary["kept"]
+            kept = D.Kept(self.koff.cpu().numpy().view(np.uint64), self.ksubs[:k].cpu().numpy().view(np.uint32),
+                          self.kfils[:k].cpu().numpy().view(np.uint32), self.kopts[:k].cpu().numpy(),
+                          self.kids[:k].cpu().numpy().view(np.uint32))
+        t = self.total
+        return D.Enriched(self.opts[:t].cpu().numpy(), self.subids[:t].cpu().numpy().view(np.uint32), summary, kept)
+
+
+def run_sync(D, t, case, compact, **kw):
+    b = DeviceBatch(D, case, compact, **kw)
+    return b.result(D, t.enrich_device(b.args))
+
+
+def run_async(D, t, case, compact, **kw):
+    import torch
+    b = DeviceBatch(D, case, compact, **kw)
+    stream = torch.cuda.Stream(device=DEV)
+    stream.wait_stream(torch.cuda.current_stream())  # the buffers were filled there
+    with torch.cuda.stream(stream):
+        t.enrich_device_async(b.args, b.summary.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    return b.result(D)
+
+
+def all_forms(D, t, case):
+    """Every device entry point, annotate-only and compacting, exact against the restatement and
+    identical to the host evaluator."""
+    for compact in (False, True):
+        host = t.enrich_host(*case.batch, compact=compact)
+        C.check(case, host, compact)
+        for got in (t.enrich_packed(*case.batch, compact=compact), run_sync(D, t, case, compact),
+                    run_async(D, t, case, compact)):
+            C.check(case, got, compact)
+            assert got.opts.tolist() == host.opts.tolist() and got.summary == host.summary
+
+
+def test_truth_table(D):
+    case = C.truth_table()
+    all_forms(D, case.load(D.SubOpts(0)), case)
+
+
+@pytest.mark.parametrize("name, mode", C.SHAPE_CASES)
+def test_shapes(D, name, mode):
+    """0 deliveries (n = 0 and n = 3), 1, the wave (63 / 64 / 65) and tile (255 / 256 / 257)
+    boundaries, and a 10 000-delivery message between empty ones over 40 tiles; mixed,
+    all-dropped and none-dropped."""
+    case = C.shape(name, mode)
+    all_forms(D, case.load(D.SubOpts(0)), case)
+
+
+FUZZ_DROPPED = 21433  # of 146858: what the restatement drops, fixed so a degenerate generator cannot pass
+
+
+@pytest.mark.parametrize("pct", [50, 90])
+def test_fuzz(D, pct):
+    case = C.fuzz()
+    s = case.reference()["summary"]
+    assert s[1] == 146858 and s[3] == FUZZ_DROPPED and 0.05 < s[3] / s[1] < 0.60
+    t = D.SubOpts(0)
+    t.set_tuning("max_load_pct", pct)
+    case.load(t)
+    st = t.stats()
+    assert st["n_entries"] == C.FUZZ_ENTRIES and st["n_slots"] == -(-C.FUZZ_ENTRIES * 100 // pct)
+    all_forms(D, t, case)
+
+
+@pytest.mark.parametrize("form", ["packed", "sync", "async"])
+def test_kept_overflow(D, form):
+    """cap_kept one short: summary bit 0, complete kept_offsets, the kept arrays untouched."""
+    from emqx_amd import _lib
+    case = C.shape("257", "mixed")
+    t = case.load(D.SubOpts(0))
+    ref = case.reference()
+    kept = ref["summary"][2]
+    if form == "packed":
+        with pytest.raises(_lib.EngineError) as e:
+            t.enrich_packed(*case.batch, compact=True, cap_kept=kept - 1)
+        assert e.value.code == _lib.EMQX_EOVERFLOW and e.value.needed == kept and e.value.summary["flags"] == 1
+        assert e.value.kept_offsets.tolist() == ref["kept"][0]
+        return
+    import torch
+    b = DeviceBatch(D, case, True, cap_kept=kept - 1)
+    if form == "sync":
+        with pytest.raises(_lib.EngineError) as e:
+            t.enrich_device(b.args)
+        assert e.value.code == _lib.EMQX_EOVERFLOW and e.value.needed == kept
+        summary = e.value.summary
+    else:
+        t.enrich_device_async(b.args, b.summary.data_ptr())
+        torch.cuda.synchronize()
+        summary = dict(zip(D.SUMMARY, b.summary.cpu().numpy().view(np.uint64).tolist()))
+    assert [summary[k] for k in D.SUMMARY] == [1] + ref["summary"][1:]
+    assert b.koff.cpu().numpy().tolist() == ref["kept"][0]
+    assert b.opts.cpu().numpy().tolist() == ref["opts"]
+    for x in (b.ksubs, b.kfils, b.kids):
+        assert (x.cpu().numpy().view(np.uint32) == 0x5A5A5A5A).all()
+    assert (b.kopts.cpu().numpy() == SENTINEL).all()
+
+
+@pytest.mark.parametrize("form", ["sync", "async"])
+def test_input_refused(D, form):
+    """offsets[n] > cap_in (the fan-out in front overflowed): summary bit 1, nothing else written."""
+    from emqx_amd import _lib
+    import torch
+    case = C.shape("257", "mixed")
+    t = case.load(D.SubOpts(0))
+    b = DeviceBatch(D, case, True, cap_in=256)
+    if form == "sync":
+        with pytest.raises(_lib.EngineError) as e:
+            t.enrich_device(b.args)
+        assert e.value.code == _lib.EMQX_EINVAL
+        summary = e.value.summary
+    else:
+        t.enrich_device_async(b.args, b.summary.data_ptr())
+        torch.cuda.synchronize()
+        summary = dict(zip(D.SUMMARY, b.summary.cpu().numpy().view(np.uint64).tolist()))
+    assert [summary[k] for k in D.SUMMARY] == [2, 257, 0, 0, 0, 0, 0, 0]
+    for x in (b.opts, b.kopts):
+        assert (x.cpu().numpy() == SENTINEL).all()
+    for x in (b.subids, b.ksubs, b.kfils, b.kids):
+        assert (x.cpu().numpy().view(np.uint32) == 0x5A5A5A5A).all()
+    assert (b.koff.cpu().numpy().view(np.uint64) == 0x5A5A5A5A5A5A5A5A).all()
+
+
+def test_wild_device_offsets_stay_in_bounds(D):
+    """Offsets that decrease and exceed the count (only their last entry is within cap_in): the
+    call completes, and nothing outside the first offsets[n] deliveries is written."""
+    import torch
+    case = C.shape("257", "mixed")
+    t = case.load(D.SubOpts(0))
+    b = DeviceBatch(D, case, True)
+    b.ins[0].copy_(dev([0, 900, 5, 1 << 40, 2, 200], np.uint64))
+    t.enrich_device_async(b.args, b.summary.data_ptr())
+    torch.cuda.synchronize()
+    s = b.summary.cpu().numpy().view(np.uint64).tolist()
+    assert s[0] == 0 and s[1] == 200 and s[2] + s[3] == 200
+    assert (b.opts[200:].cpu().numpy() == SENTINEL).all() and (b.kopts[s[2]:].cpu().numpy() == SENTINEL).all()
+    assert (b.opts[:200].cpu().numpy() != SENTINEL).all()
+
+
+def test_async_call_keeps_its_snapshot_across_a_commit(D):
+    import torch
+    case = C.fuzz()
+    t = case.load(D.SubOpts(0))
+    stream = torch.cuda.Stream(device=DEV)
+    calls = [DeviceBatch(D, case, True) for _ in range(3)]
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        for b in calls:
+            t.enrich_device_async(b.args, b.summary.data_ptr(), stream=stream.cuda_stream)
+    # remove half of the entries while the calls may still be running: they answer from the old snapshot
+    half = case.entries[::2]
+    t.remove([e[0] for e in half], [e[1] for e in half])
+    t.commit()
+    stream.synchronize()
+    for b in calls:
+        C.check(case, b.result(D), True)
+    after = C.Case("fuzz_half", case.entries[1::2], *case.batch)
+    got = run_async(D, t, after, True)
+    C.check(after, got, True)
+    assert got.summary["no_subopts"] > case.reference()["summary"][4]
+    assert t.stats()["n_entries"] == len(case.entries) - len(half)
+
+
+def _broker_pair():
+    from emqx_amd.fanout import Broker
+    from oracle import broker_ref as BR
+    filters = [b"sensor/+/temp", b"sensor/#", b"#", b"+/+/temp", b"sensor/1/temp", b"a/b", b"a/+", b"$SYS/#"]
+    b, rb, sessions = Broker(0, node=BR.NODE, strategy="hash_clientid"), BR.Broker(), {}
+    rng = np.random.default_rng(5)
+    made = []
+    for c in range(24):
+        sub = "c%d" % c
+        for f in rng.choice(len(filters), size=4, replace=False).tolist():
+            share = b"g" if rng.random() < 0.25 else None
+            opts = None
+            if rng.random() < 0.8:
+                opts = {"qos": int(rng.integers(0, 3)), "nl": int(rng.random() < 0.6), "rap": int(rng.integers(0, 2)),
+                        "upgrade_qos": c % 3 == 0}
+                if rng.random() < 0.5:
+                    opts["subid"] = int(rng.integers(1, 1000))
+            b.subscribe(filters[f], sub, share, subopts=opts)
+            rb.subscribe(filters[f], sub, share)
+            if opts is not None:  # the session map is keyed by the filter without the share prefix
+                s = sessions.setdefault(sub, {"subscriptions": {}, "upgrade_qos": opts["upgrade_qos"]})
+                s["subscriptions"][filters[f]] = {k: v for k, v in opts.items() if k != "upgrade_qos"}
+            made.append((filters[f], sub, share))
+    # a few unsubscribes: their options go with them
+    for topic, sub, share in made[::9]:
+        b.unsubscribe(topic, sub, share)
+        rb.unsubscribe(topic, sub, share)
+        sessions.get(sub, {"subscriptions": {}})["subscriptions"].pop(topic, None)
+    return b, rb, sessions, BR
+
+
+def _expected_rows(rb, sessions, BR, messages, keys):
+    """oracle/broker_ref.py's deliveries, then the restatement per delivery."""
+    rows = []
+    for (topic, qos, retain, frm), key in zip(messages, keys):
+        row = []
+        for filt, sub, shared in rb.publish(topic, key, BR.HASH_CLIENTID):
+            sess = sessions.get(sub, {"subscriptions": {}, "upgrade_qos": False})
+            d = (filt, R.message(qos, 1 if retain else 0, frm))
+            if R.ignore_local([d], sub, sess) == []:
+                continue
+            out = R.enrich(d, sess)
+            row.append((filt, sub, shared, out["qos"], bool(out["flags"].get("retain")), bool(out["flags"].get("nl")),
+                        out["headers"].get("properties", {}).get("Subscription-Identifier")))
+        rows.append(row)
+    return rows
+
+
+def _messages(n):
+    rng = np.random.default_rng(6)
+    topics = [b"sensor/1/temp", b"sensor/2/temp", b"sensor/2/hum", b"a/b", b"a/c", b"x/y/temp", b"$SYS/up", b"none"]
+    msgs = []
+    for _ in range(n):
+        frm = "c%d" % rng.integers(0, 24) if rng.random() < 0.7 else None
+        msgs.append((topics[int(rng.integers(0, len(topics)))], int(rng.integers(0, 3)), bool(rng.integers(0, 2)), frm))
+    return msgs, rng.integers(0, 1 << 20, size=n).tolist()
+
+
+def test_publish_messages(D):
+    b, rb, sessions, BR = _broker_pair()
+    msgs, keys = _messages(300)
+    got = b.publish_messages(msgs, keys=keys)
+    want = _expected_rows(rb, sessions, BR, msgs, keys)
+    assert sum(map(len, want)) > 1000
+    for g, w, m in zip(got, want, msgs):
+        assert sorted(map(repr, g)) == sorted(map(repr, w)), m
+    plain = b.publish_batch([m[0] for m in msgs], keys)
+    assert sum(map(len, plain)) > sum(map(len, got)), "No Local drops something"
+
+
+def test_chain_match_fanout_enrich_on_one_stream(D):
+    """emqx_match_batch_device_async -> emqx_fanout_batch_device_async ->
+    emqx_deliver_enrich_batch_device_async on one stream, no host read in between."""
+    import torch
+    from emqx_amd.engine import pack
+    b, rb, sessions, BR = _broker_pair()
+    b._sync()
+    n = 2048
+    msgs, keys = _messages(n)
+    buf, offs = pack([m[0] for m in msgs])
+    d_buf, d_off = dev(buf, np.uint8), dev(offs, np.uint64)
+    d_keys = dev(keys, np.uint32)
+    d_qos, d_flags = dev([m[1] for m in msgs], np.uint8), dev([1 if m[2] else 0 for m in msgs], np.uint8)
+    d_from = dev([R.NO_SENDER if m[3] is None else b._sub_ids[m[3]] for m in msgs], np.uint32)
+    cap = 64 * n
+    e = b.router.engine
+    z = lambda k, dt: torch.zeros(k, dtype=dt, device=DEV)  # noqa: E731
+    d_moff, d_mids, d_ms = z(n + 1, torch.int64), z(cap, torch.int32), z(e.SUMMARY_WORDS, torch.int64)
+    d_doff, d_subs, d_fils, d_fs = z(n + 1, torch.int64), z(cap, torch.int32), z(cap, torch.int32), z(4, torch.int64)
+    d_out, d_ids = z(cap, torch.uint8), z(cap, torch.int32)
+    d_koff, k_subs, k_fils, k_opts, k_ids = (z(n + 1, torch.int64), z(cap, torch.int32), z(cap, torch.int32),
+                                             z(cap, torch.uint8), z(cap, torch.int32))
+    d_sum = z(8, torch.int64)
+    args = D.SubOpts.batch(d_doff.data_ptr(), d_subs.data_ptr(), d_fils.data_ptr(), n, cap, d_qos.data_ptr(),
+                           d_flags.data_ptr(), d_from.data_ptr(), d_out.data_ptr(), d_ids.data_ptr(), d_koff.data_ptr(),
+                           k_subs.data_ptr(), k_fils.data_ptr(), k_opts.data_ptr(), k_ids.data_ptr(), cap)
+    stream = torch.cuda.Stream(device=DEV)
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        e.match_device_async(d_buf.data_ptr(), d_off.data_ptr(), n, d_moff.data_ptr(), d_mids.data_ptr(), cap,
+                             d_ms.data_ptr(), mode=0, stream=stream.cuda_stream)
+        b.subs.fanout_device_async(b.strategy, d_moff.data_ptr(), d_mids.data_ptr(), n, cap, d_keys.data_ptr(),
+                                   d_doff.data_ptr(), d_subs.data_ptr(), d_fils.data_ptr(), cap, d_fs.data_ptr(),
+                                   stream=stream.cuda_stream)
+        b.opts.enrich_device_async(args, d_sum.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    assert int(d_ms[0]) == 0 and int(d_fs[0]) == 0, "the match and the fan-out completed in one pass"
+    s = d_sum.cpu().numpy().view(np.uint64).tolist()
+    assert s[0] == 0 and s[1] == int(d_fs[1])
+    want = _expected_rows(rb, sessions, BR, msgs, keys)
+    assert s[2] == sum(map(len, want)) and s[3] > 0
+    off = d_koff.cpu().numpy()
+    subs, fils = k_subs.cpu().numpy().view(np.uint32), k_fils.cpu().numpy().view(np.uint32)
+    opts, ids = k_opts.cpu().numpy(), k_ids.cpu().numpy().view(np.uint32)
+    names = b.router._names
+    for i in range(n):
+        got = [(names[int(fils[j]) & 0x3FFFFFFF], b._subs_by_id[int(subs[j])], bool(int(fils[j]) & R.SHARED_BIT),
+                int(opts[j]) & 3, bool(opts[j] & R.OUT_RETAIN), bool(opts[j] & R.OUT_NL), int(ids[j]) or None)
+               for j in range(int(off[i]), int(off[i + 1]))]
+        assert sorted(map(repr, got)) == sorted(map(repr, want[i])), msgs[i]
+    rows = b.publish_messages(msgs, keys=keys)
+    for g, w in zip(rows, want):
+        assert sorted(map(repr, g)) == sorted(map(repr, w))
