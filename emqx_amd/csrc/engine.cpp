@@ -80,6 +80,7 @@ struct Snapshot {
   TableView tv{};
   uint64_t n_nodes = 0, n_slots = 0, n_words = 0, bytes = 0;
   uint32_t max_depth = 0;
+  bool narrow = false;  // every id the tables can report fits the 4-byte slab entry (layout.h)
 };
 
 // Writer-side state of incremental commits (under emqx_engine::writer): the host image of
@@ -109,12 +110,13 @@ struct Workspace {
   hipStream_t stream = nullptr;
   hipStream_t last_stream = nullptr;  // stream of the last call enqueued with this workspace
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evk = nullptr;
-  uint64_t cap_n = 0, cap_tiles = 0, cap_slab = 0;
-  uint32_t slab_per_tile = 256;
+  uint64_t cap_n = 0, cap_tiles = 0;
+  uint64_t cap_slab = 0;            // bytes
+  uint32_t slab_per_tile = 256;     // entries, of either width
   uint32_t* counts = nullptr;
   uint32_t* deferred = nullptr;
   uint32_t* deep_rank = nullptr;
-  uint64_t* slab = nullptr;
+  uint8_t* slab = nullptr;          // SlabNarrow or SlabWide entries, as the call's snapshot asks
   uint32_t* tile_fill = nullptr;
   uint64_t* tile_defer = nullptr;
   uint2* spill = nullptr;
@@ -284,6 +286,11 @@ int full_commit(emqx_engine* e) {
   s->n_words = ht.n_words;
   s->max_depth = ht.max_depth;
   s->bytes = dt->bytes();
+  // the slab entry width of every call on these tables: the largest id they can come to report
+  // (a deleted filter keeps its id for a revival; live_commit keeps later ids within it)
+  uint32_t max_id = 0;
+  for (uint32_t x : e->store.ext) max_id = std::max(max_id, x);
+  s->narrow = slab_narrow_ok(max_id);
 
   LiveState& d = e->ls;
   d.device = e->device;
@@ -322,6 +329,12 @@ int live_commit(emqx_engine* e) {
     // filters of an empty build), a fresh line-packed, perfect-hashed build serves it better
     return EMQX_NEED_FULL;
   }
+
+  // tables whose calls write 4-byte slab entries take no id beyond that format: a walk that
+  // overlaps this commit would pack it.  Fresh tables (a full build) choose their format anew.
+  if (e->snap->narrow)
+    for (uint32_t id : ids)
+      if (!slab_narrow_ok(fs.ext[id])) return EMQX_NEED_FULL;
 
   const uint64_t nw0 = d.vocab->n_words(), arena0 = d.vocab->arena.size();
   auto th0 = std::chrono::steady_clock::now();
@@ -429,7 +442,8 @@ void release_ws(emqx_engine* e, Workspace* w) {
   e->free_ws.push_back(w);
 }
 
-int ensure_ws(Workspace* w, uint64_t n) {
+// entry_bytes: the slab entry width of the call (sizeof SlabNarrow::T or SlabWide::T).
+int ensure_ws(Workspace* w, uint64_t n, uint64_t entry_bytes) {
   if (!w->stream) {
     HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&w->ev0));
@@ -467,7 +481,7 @@ int ensure_ws(Workspace* w, uint64_t n) {
     HIP_TRY(dalloc(w->spill, cap * w->spill_cap));
     w->cap_tiles = cap;
   }
-  const uint64_t need_slab = std::max<uint64_t>(ntiles, 1) * w->slab_per_tile;
+  const uint64_t need_slab = std::max<uint64_t>(ntiles, 1) * w->slab_per_tile * entry_bytes;
   if (need_slab > w->cap_slab) {
     const uint64_t cap = need_slab;
     HIP_TRY(dalloc(w->slab, cap));
@@ -546,6 +560,7 @@ MatchArgs match_args(emqx_engine* e, const Snapshot& snap, Workspace* w, uint32_
   a.slab_cap = w->slab_per_tile;
   a.counts = w->counts;
   a.slab = w->slab;
+  a.narrow = snap.narrow ? 1u : 0u;
   a.tile_fill = w->tile_fill;
   a.tile_defer = w->tile_defer;
   a.spill = w->spill;
@@ -574,10 +589,14 @@ MatchArgs match_args(emqx_engine* e, const Snapshot& snap, Workspace* w, uint32_
   return a;
 }
 
+uint64_t slab_entry_bytes(const Snapshot& snap) {
+  return snap.narrow ? sizeof(SlabNarrow::T) : sizeof(SlabWide::T);
+}
+
 int enqueue_match(emqx_engine* e, const Snapshot& snap, Workspace* w, uint32_t mode, const uint8_t* d_tbytes,
                   const uint64_t* d_toffs, uint64_t n, uint64_t* d_out_off, uint32_t* d_out_ids, uint64_t cap,
                   uint64_t* summary, hipStream_t s) {
-  int rc = ensure_ws(w, n);
+  int rc = ensure_ws(w, n, slab_entry_bytes(snap));
   if (rc != EMQX_OK) return rc;
   MatchArgs a = match_args(e, snap, w, mode, d_tbytes, d_toffs, n, d_out_off, d_out_ids, cap, summary);
   const bool ordered = use_order(e, snap, n);
@@ -726,16 +745,17 @@ int enqueue_small(emqx_engine* e, const Snapshot& snap, Workspace* w, uint32_t m
                   uint32_t* h_out_ids, uint64_t h_cap, const SmallFanout* f, hipStream_t s) {
   // the workspace sized for SMALL_WAVES tiles whatever n: the kernel's tiles are ceil(n / 16)
   // topics wide, so a batch of a few topics still spans up to 16 slab tiles
-  int rc = ensure_ws(w, SMALL_MAX_N);
+  int rc = ensure_ws(w, SMALL_MAX_N, sizeof(SlabWide::T));  // the small-batch kernel's entries are wide
   if (rc != EMQX_OK) return rc;
   SmallArgs sa{};
   sa.m = match_args(e, snap, w, mode, d_tbytes, d_toffs, n, d_out_off, d_out_ids, cap, summary);
   sa.m.diag = nullptr;
+  sa.m.narrow = 0;
   sa.h_tbytes = h_tbytes;
   sa.h_toffs = h_toffs;
   sa.nbytes = nbytes;
   sa.tt = static_cast<uint32_t>((n + SMALL_WAVES - 1) / SMALL_WAVES);
-  sa.slab_tiles = static_cast<uint32_t>(std::min<uint64_t>(w->cap_slab / w->slab_per_tile, w->cap_tiles));
+  sa.slab_tiles = static_cast<uint32_t>(std::min<uint64_t>(w->cap_slab / (sizeof(SlabWide::T) * w->slab_per_tile), w->cap_tiles));
   sa.h_out_off = h_out_off;
   sa.h_out_ids = h_out_ids;
   sa.h_cap = h_cap;
@@ -840,7 +860,7 @@ int hb_enqueue(emqx_host_batch* b) {
   if (nbytes) HIP_TRY(hipMemcpyAsync(p->d_tbytes, b->topic_bytes, nbytes, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(p->d_toffs, b->topic_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   Workspace* w = acquire_ws(e, s);
-  int rc = ensure_ws(w, n);
+  int rc = ensure_ws(w, n, slab_entry_bytes(*p->snap));
   if (rc == EMQX_OK)
     rc = enqueue_match(e, *p->snap, w, p->mode, p->d_tbytes, p->d_toffs, n, p->d_out_off, p->d_out_ids, b->cap_ids,
                        sum_dev, s);
@@ -867,7 +887,7 @@ int hb_wait(emqx_host_batch* b) {
   uint64_t total = p->summary[SUM_TOTAL];
   if (flags & SUM_F_RETRY) {  // a scratch area overflowed: the synchronous path grows it and reruns
     Workspace* w = acquire_ws(p->e, p->stream);
-    int rc = ensure_ws(w, b->n);
+    int rc = ensure_ws(w, b->n, slab_entry_bytes(*p->snap));
     if (rc == EMQX_OK)
       rc = run_match(p->e, *p->snap, w, p->mode, p->d_tbytes, p->d_toffs, b->n, p->d_out_off, p->d_out_ids,
                      b->cap_ids, &total, p->stream);
@@ -1047,7 +1067,7 @@ int emqx_match_batch_device(emqx_engine* e, uint32_t mode, const uint8_t* d_topi
   HIP_TRY(hipSetDevice(e->device));
   auto snap = current(e);
   Workspace* w = acquire_ws(e, static_cast<hipStream_t>(stream));
-  int rc = ensure_ws(w, n);
+  int rc = ensure_ws(w, n, slab_entry_bytes(*snap));
   if (rc == EMQX_OK) {
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : w->stream;
     if (!stream && after_null_stream(s) != hipSuccess) rc = EMQX_EDEVICE;
@@ -1067,7 +1087,7 @@ int emqx_match_batch_device_async(emqx_engine* e, uint32_t mode, const uint8_t* 
   HIP_TRY(hipSetDevice(e->device));
   auto snap = current(e);
   Workspace* w = acquire_ws(e, static_cast<hipStream_t>(stream));
-  int rc = ensure_ws(w, n);
+  int rc = ensure_ws(w, n, slab_entry_bytes(*snap));
   if (rc == EMQX_OK) {
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : w->stream;
     if (!stream && after_null_stream(s) != hipSuccess) rc = EMQX_EDEVICE;

@@ -72,7 +72,9 @@ struct MatchArgs {
   uint32_t mode;
   uint32_t slab_cap;       // entries per tile
   uint32_t* counts;        // [n]
-  uint64_t* slab;          // [ntiles * slab_cap]  (topic_local << 32) | fid
+  void* slab;              // [ntiles * slab_cap] entries: SlabNarrow (4 B) when `narrow`, else SlabWide (layout.h)
+  uint32_t narrow;         // the snapshot's ids fit the narrow entry (batched fast path; the small-batch
+                           // kernel always writes wide entries)
   uint32_t* tile_fill;     // [ntiles]
   uint64_t* tile_defer;    // [ntiles]
   uint32_t* ctrl;          // [CTRL_WORDS]

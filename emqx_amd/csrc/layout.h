@@ -63,8 +63,10 @@ constexpr uint32_t PH_MAX_CAPLOG = 15;
 //     in place of child_base and litf — the common leaf emission needs no second load;
 //   * for a child with edges and one filter id (META_XFID), which carries it in litf; its
 //     literal filter shrinks to an 8-bit fingerprint / Bloom mask in the meta's top byte.
-// For the others the walk emits the reference 2i + kind and the scatter kernel resolves it,
-// so a probe moves 16 B and the walk never waits on an id.
+// For the others the fast walk loads fids[2i + kind] itself, on the lanes that need it, and
+// writes the id one step later (the load travels with the next step's probes), so a probe
+// moves 16 B and the walk never waits on an id.  The deep path emits the reference 2i + kind
+// and its scatter resolves it.
 struct alignas(16) EdgeSlot {
   uint32_t wid;         // key (WID_NONE = empty)
   uint32_t child_base;  // first slot of the child's edge array  | edgeless child: hash_fid
@@ -75,6 +77,33 @@ struct alignas(16) EdgeSlot {
 };
 static_assert(sizeof(EdgeSlot) == 16, "EdgeSlot must be 16 bytes");
 constexpr uint64_t MAX_SLOTS = (1ull << 31) - 1;  // references 2i + kind fit 32 bits
+
+// Fast-slab entries (match_kernels.hip: the walk's emissions, read back by the scatter): the
+// owner — the topic's index in its tile, 6 bits — and a final filter id.
+//   SlabWide    8 B  owner << 32 | id        any id
+//   SlabNarrow  4 B  owner << 26 | id        ids below SLAB_NARROW_IDS
+// The all-ones word is the scatter's padding marker in both.  In the narrow format that word
+// is owner 63 with id 2^26 - 1, so the narrow id space ends one short of 2^26; the wide
+// format's marker has owner bits no entry carries.  The host picks the format per full build
+// (slab_narrow_ok over every id the table can report) and an incremental commit that would
+// bring in a larger id falls back to a full build.
+constexpr uint32_t SLAB_NARROW_ID_BITS = 26;
+constexpr uint32_t SLAB_NARROW_IDS = (1u << SLAB_NARROW_ID_BITS) - 1u;  // ids must be below this
+EMQX_HD bool slab_narrow_ok(uint32_t max_id) { return max_id < SLAB_NARROW_IDS; }
+struct SlabWide {
+  typedef uint64_t T;
+  static constexpr T PAD = ~0ull;
+  static EMQX_HD T make(uint32_t owner, uint32_t id) { return (static_cast<uint64_t>(owner) << 32) | id; }
+  static EMQX_HD uint32_t owner(T e) { return static_cast<uint32_t>(e >> 32) & 63u; }
+  static EMQX_HD uint32_t id(T e) { return static_cast<uint32_t>(e); }
+};
+struct SlabNarrow {
+  typedef uint32_t T;
+  static constexpr T PAD = ~0u;
+  static EMQX_HD T make(uint32_t owner, uint32_t id) { return (owner << SLAB_NARROW_ID_BITS) | id; }
+  static EMQX_HD uint32_t owner(T e) { return e >> SLAB_NARROW_ID_BITS; }
+  static EMQX_HD uint32_t id(T e) { return e & ((1u << SLAB_NARROW_ID_BITS) - 1u); }
+};
 
 // One in-place rewrite of an existing slot by an incremental commit (live_trie.cpp): the
 // slot's new content and its two filter ids.

@@ -15,16 +15,18 @@
 //              flight together — probes each node's '+' edge (slot 0, no search) and its
 //              literal edge (perfect hash or 2-slot bucket), pushes the children and emits
 //              the found children's '#' and terminal filter ids (inline in the slot of an
-//              edgeless child, else a fids[] reference the scatter resolves: the walk never
-//              waits on an id); pushes and emissions are stream-compacted with wave ballots
-//              + popcount prefix sums.
+//              edgeless child, else loaded from fids[] on the lanes that need one and written
+//              a step later, so the walk never waits on an id); pushes and emissions are
+//              stream-compacted with wave ballots + popcount prefix sums.
 //              The stack is LIFO, which bounds it by ~64*K x levels whatever the frontier
 //              width.  No MFMA: this is pointer chasing.
-//     phase C  per-topic counts + a per-tile slab of (topic, filter id or reference) entries.
+//     phase C  per-topic counts + a per-tile slab of (topic, filter id) entries, 4 or 8 bytes
+//              each (layout.h SlabNarrow / SlabWide, chosen per snapshot on the host).
 //   match_deep_kernel  topics that did not fit the fast path's LDS budget (very deep
 //              topics, or a frontier that overflowed the stack): one wavefront per topic,
 //              word ids and stack in global scratch.
-//   scan / scatter     counts -> CSR offsets; slab entries (references resolved) -> out_ids.
+//   scan / scatter     counts -> CSR offsets; slab entries -> out_ids (the deep slab's
+//              references resolved).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -116,8 +118,9 @@ __device__ __forceinline__ Slot load_slot(const EdgeSlot* edges, uint32_t i) {
   return s;
 }
 
-// Slab / deep-slab entry: owner << 32 | value.  The value is a filter id, or — with
-// ENTRY_REF set — a fids[] reference the scatter kernels resolve.
+// Deep-slab entry: owner << 32 | value.  The value is a filter id, or — with ENTRY_REF set —
+// a fids[] reference scatter_deep_kernel resolves.  (Fast-slab entries hold final ids:
+// layout.h SlabWide / SlabNarrow.)
 constexpr uint64_t ENTRY_REF = 1ull << 63;
 
 // Emission value of a found child's '#' (kind 0) or terminal (kind 1) filter: the id itself
@@ -130,6 +133,15 @@ __device__ __forceinline__ uint64_t emit_value(const Slot& s, uint32_t kind) {
 
 __device__ __forceinline__ uint32_t resolve_entry(const TableView& tv, uint64_t e) {
   return (e & ENTRY_REF) ? tv.fids[static_cast<uint32_t>(e)] : static_cast<uint32_t>(e);
+}
+
+// Fast path: a found child's ids live in fids[] (a child with edges that carries no id in
+// its slot); otherwise the slot holds the id asked for (emit_value's first two cases).
+__device__ __forceinline__ bool ids_in_fids(const Slot& s) {
+  return (s.a.z & (META_HAS_EDGES | META_XFID)) == META_HAS_EDGES;
+}
+__device__ __forceinline__ uint32_t slot_id(const Slot& s, uint32_t kind) {
+  return ((s.a.z & META_HAS_EDGES) || kind) ? s.a.w : s.a.y;
 }
 
 __device__ __forceinline__ Slot empty_slot() {
@@ -576,7 +588,8 @@ constexpr uint32_t PA_WIDS = 192;
 // NH: each item's next word id is read from LDS before its probe loads are issued (in flight
 // with them), not after they return (round 5, -0.9 % on config B; FAST_K1_S384N keeps the old
 // order for the A/B harness).
-template <int STACK_CAP, int WID_CAP, int K, bool DIAG, bool RL = false, int PA = 0, bool NH = true>
+// E: the slab entry format (layout.h SlabWide / SlabNarrow).
+template <int STACK_CAP, int WID_CAP, int K, bool DIAG, bool RL = false, int PA = 0, bool NH = true, class E = SlabWide>
 __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP, WID_CAP>& L, uint64_t tile,
                                           uint32_t tt, const uint4* rl = nullptr, uint32_t rsz = 0) {
   static_assert(STACK_CAP >= 4 * 64 * K && STACK_CAP % 128 == 0, "stack must hold 4 pops");
@@ -804,7 +817,7 @@ __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP,
   const uint64_t clk1 = DIAG ? wall_clock64() : 0;
 
   // ---- phase B: pooled frontier walk ------------------------------------------------
-  uint64_t* slab = a.slab + tile * a.slab_cap;
+  typename E::T* slab = static_cast<typename E::T*>(a.slab) + tile * a.slab_cap;
   uint2* spill = a.spill + tile * a.spill_cap;
   const uint32_t cap = a.slab_cap;
   const uint32_t mode = a.mode;
@@ -840,9 +853,8 @@ __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP,
     const uint32_t c = (e0 ? 1u : 0u) + (e1 ? 1u : 0u);
     uint32_t tot;
     uint32_t pos = wave_prefix<2>(c, lane, &tot);
-    const uint64_t tag = static_cast<uint64_t>(lane) << 32;
-    if (e0) { if (pos < cap) slab[pos] = tag | tv.root_hash_fid; ++pos; }
-    if (e1) { if (pos < cap) slab[pos] = tag | g1; ++pos; }
+    if (e0) { if (pos < cap) slab[pos] = E::make(lane, tv.root_hash_fid); ++pos; }
+    if (e1) { if (pos < cap) slab[pos] = E::make(lane, g1); ++pos; }
     if (c) L.cnt[lane] = c;
     cursor = tot;
     uint32_t ptot;
@@ -852,6 +864,37 @@ __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP,
     maxtop = top;
     wave_sync();
   }
+
+  // Ids read from fids[]: the loads are issued at the end of a step, behind its other
+  // emissions, and their entries are written after the next step's probe loads have returned
+  // (or after the loop), so no step waits for an id.  Per item: the {'#', terminal} id pairs
+  // of the literal and the '+' child, the slab position of the item's first emission, and
+  // pend = emission flags (bits 0..3: literal '#', literal terminal, '+' '#', '+' terminal) |
+  // pair pending (bit 4 literal, bit 5 '+') | topic << 8.
+  uint2 pv[2 * K];
+  uint32_t ppos[K], pend[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    pv[2 * k] = pv[2 * k + 1] = make_uint2(0, 0);
+    ppos[k] = 0;
+    pend[k] = 0;
+  }
+  auto flush_pending = [&]() {
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) any = any || (pend[k] & 0x30u);
+    if (!__ballot(any)) return;  // wave-uniform: most steps hold no fids[] id
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const uint32_t f = pend[k], ptl = f >> 8;
+      uint32_t q = ppos[k];
+      if (f & 1u) { if ((f & 0x10u) && q < cap) slab[q] = E::make(ptl, pv[2 * k].x); ++q; }
+      if (f & 2u) { if ((f & 0x10u) && q < cap) slab[q] = E::make(ptl, pv[2 * k].y); ++q; }
+      if (f & 4u) { if ((f & 0x20u) && q < cap) slab[q] = E::make(ptl, pv[2 * k + 1].x); ++q; }
+      if (f & 8u) { if ((f & 0x20u) && q < cap) slab[q] = E::make(ptl, pv[2 * k + 1].y); ++q; }
+      pend[k] = 0;
+    }
+  };
 
   if (DIAG && a.diag_stop) top = 0;  // phase A alone (diagnostic counter passes)
   constexpr uint32_t POP = 64u * K;
@@ -933,6 +976,13 @@ __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP,
     }
     probe_items<K, RL>(tv.edges, tv.plus_mask, ibase, hpar, isph, cpy, needL, wid, needP, lit, fL, pls, fP, dg[4], rl,
                        rsz, tv.root_base);
+    // The previous step's fids[] loads came back under the probes' wait.  The empty asm uses
+    // their registers right there, on every path, so the compiler counts the loads as landed
+    // and puts no wait in front of this step's (it would guard the registers' reuse otherwise,
+    // and the second load of a step would wait for the first).
+#pragma unroll
+    for (int k = 0; k < 2 * K; ++k) asm volatile("" : "+v"(pv[k].x), "+v"(pv[k].y));
+    flush_pending();
     if (DIAG) {
 #pragma unroll
       for (int k = 0; k < K; ++k) {
@@ -992,11 +1042,19 @@ __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP,
       uint32_t pos = cursor + wave_prefix<ceil_log2(4 * K + 1)>(ecount, lane, &tot);
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        const uint64_t tag = static_cast<uint64_t>(tl[k]) << 32;
-        if (eLh[k]) { if (pos < cap) slab[pos] = tag | emit_value(lit[k], 0); ++pos; }
-        if (eLt[k]) { if (pos < cap) slab[pos] = tag | emit_value(lit[k], 1); ++pos; }
-        if (ePh[k]) { if (pos < cap) slab[pos] = tag | emit_value(pls[k], 0); ++pos; }
-        if (ePt[k]) { if (pos < cap) slab[pos] = tag | emit_value(pls[k], 1); ++pos; }
+        const bool rL = (eLh[k] || eLt[k]) && ids_in_fids(lit[k]);
+        const bool rP = (ePh[k] || ePt[k]) && ids_in_fids(pls[k]);
+        if (rL) pv[2 * k] = *reinterpret_cast<const uint2*>(tv.fids + 2ull * lit[k].idx);
+        if (rP) pv[2 * k + 1] = *reinterpret_cast<const uint2*>(tv.fids + 2ull * pls[k].idx);
+        if (rL || rP) {
+          ppos[k] = pos;
+          pend[k] = (eLh[k] ? 1u : 0u) | (eLt[k] ? 2u : 0u) | (ePh[k] ? 4u : 0u) | (ePt[k] ? 8u : 0u) |
+                    (rL ? 0x10u : 0u) | (rP ? 0x20u : 0u) | (tl[k] << 8);
+        }
+        if (eLh[k]) { if (!rL && pos < cap) slab[pos] = E::make(tl[k], slot_id(lit[k], 0)); ++pos; }
+        if (eLt[k]) { if (!rL && pos < cap) slab[pos] = E::make(tl[k], slot_id(lit[k], 1)); ++pos; }
+        if (ePh[k]) { if (!rP && pos < cap) slab[pos] = E::make(tl[k], slot_id(pls[k], 0)); ++pos; }
+        if (ePt[k]) { if (!rP && pos < cap) slab[pos] = E::make(tl[k], slot_id(pls[k], 1)); ++pos; }
         if (ce[k]) atomicAdd(&L.cnt[tl[k]], ce[k]);
       }
       cursor += tot;
@@ -1005,6 +1063,7 @@ __device__ __forceinline__ void fast_tile(const MatchArgs& a, FastLds<STACK_CAP,
     wave_sync();
   }
 
+  flush_pending();  // the last step's
   // ---- phase C: per-topic counts, tile bookkeeping ---------------------------------
   wave_sync();
   if (DIAG && a.diag) {
@@ -1049,7 +1108,8 @@ constexpr uint32_t ROOT_LDS_SLOTS = 256;  // FAST_K1_S384R: root arrays up to 4 
 // (waves per SIMD asked of the compiler: 8 for K = 1, i.e. <= 64 VGPRs, which it exceeds (73, so 6
 // waves); FAST_K1_S384W7 (448 word ids) asks for 7, which its 21.5 KiB of LDS per block allows)
 constexpr int fast_waves_hint(int K, int WC) { return K == 1 ? (WC == 448 ? 7 : 8) : 5; }
-template <int WAVES, int STACK_CAP, int WID_CAP, int K, bool DIAG, bool RL = false, int PA = 0, bool NH = true>
+template <int WAVES, int STACK_CAP, int WID_CAP, int K, bool DIAG, bool RL = false, int PA = 0, bool NH = true,
+          class E = SlabWide>
 __global__ __launch_bounds__(WAVES * 64, fast_waves_hint(K, WID_CAP)) void match_fast_kernel(MatchArgs a) {
   __shared__ FastLds<STACK_CAP, WID_CAP> lds_all[WAVES];
   __shared__ uint4 rl[RL ? ROOT_LDS_SLOTS : 1];
@@ -1071,7 +1131,7 @@ __global__ __launch_bounds__(WAVES * 64, fast_waves_hint(K, WID_CAP)) void match
     const uint32_t nb = gridDim.x, x = blockIdx.x & 7u, j = blockIdx.x >> 3, q = nb >> 3, r = nb & 7u;
     blk = static_cast<uint64_t>(x) * q + min(x, r) + j;
   }
-  fast_tile<STACK_CAP, WID_CAP, K, DIAG, RL, PA, NH>(a, lds_all[wv], blk * WAVES + wv, TILE_TOPICS, rl, rsz);
+  fast_tile<STACK_CAP, WID_CAP, K, DIAG, RL, PA, NH, E>(a, lds_all[wv], blk * WAVES + wv, TILE_TOPICS, rl, rsz);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1407,8 +1467,10 @@ __global__ __launch_bounds__(GROUP_TILES) void group_reduce_kernel(MatchArgs a, 
 // Then its slab entries, 64 at a time: lanes holding the same topic find each other with six
 // ballots (one per bit of the topic index) and take ranks by popcount, and the same ballots
 // advance every topic's running position — no atomics.  Ids beyond out_cap are dropped.
+template <class E>
 __device__ __forceinline__ void scatter_tile(const MatchArgs& a, uint64_t tile, uint64_t off);
 
+template <class E>
 __global__ __launch_bounds__(256) void scatter_fast_kernel(MatchArgs a) {
   const uint32_t lane = lane_id();
   const uint32_t wv = threadIdx.x >> 6;
@@ -1430,36 +1492,38 @@ __global__ __launch_bounds__(256) void scatter_fast_kernel(MatchArgs a) {
     off = before + wave_incl_scan64(c, lane) - c;
     if (t < a.n) a.out_off[t] = off;
   }
-  scatter_tile(a, tile, off);
+  scatter_tile<E>(a, tile, off);
 }
 
 // Lane L keeps topic L's next output position in a register.  Per round of 64 entries the
 // six topic-bit ballots give each entry its rank among the round's entries of its topic and
 // each lane its topic's count in the round; positions travel by cross-lane reads.  No LDS
 // and no fence in the loop, so the id stores never hold the next round's loads back.
-// off: the output position of this lane's topic of the tile.
+// off: the output position of this lane's topic of the tile.  E: the slab's entry format; its
+// ids are final (the walk has resolved the fids[] references).
+template <class E>
 __device__ __forceinline__ void scatter_tile(const MatchArgs& a, uint64_t tile, uint64_t off) {
+  typedef typename E::T T;
   const uint32_t lane = lane_id();
   uint64_t next = off;
   const uint32_t fill = min(a.tile_fill[tile], a.slab_cap);
   const uint64_t dmask = a.tile_defer[tile];
-  const uint64_t* slab = a.slab + tile * a.slab_cap;
+  const T* slab = static_cast<const T*>(a.slab) + tile * a.slab_cap;
   const uint64_t lt = lanemask_lt(lane);
-  constexpr uint32_t U = 4;  // rounds whose slab loads and id lookups are in flight together
+  // rounds whose slab loads are in flight together: 2 KiB per wave in either format
+  constexpr uint32_t U = 32 / sizeof(T);
   for (uint32_t i0 = 0; i0 < fill; i0 += 64 * U) {
-    uint64_t e[U];
-    uint32_t id[U];
+    T e[U];
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
       const uint32_t i = i0 + 64 * u + lane;
-      e[u] = i < fill ? slab[i] : ~0ull;
+      e[u] = i < fill ? slab[i] : E::PAD;
     }
 #pragma unroll
-    for (uint32_t u = 0; u < U; ++u) id[u] = e[u] != ~0ull ? resolve_entry(a.tv, e[u]) : 0u;
-#pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
-      const uint32_t tl = static_cast<uint32_t>(e[u] >> 32) & 63u;
-      const bool keep = e[u] != ~0ull && !((dmask >> tl) & 1ull);
+      if (i0 + 64 * u >= fill) break;  // wave-uniform: the rounds past the tile's last entry
+      const uint32_t tl = E::owner(e[u]);
+      const bool keep = e[u] != E::PAD && !((dmask >> tl) & 1ull);
       const uint64_t km = __ballot(keep);
       uint64_t peers = km, mine = km;
 #pragma unroll
@@ -1473,7 +1537,7 @@ __device__ __forceinline__ void scatter_tile(const MatchArgs& a, uint64_t tile, 
       const uint32_t hi = __shfl(static_cast<uint32_t>(next >> 32), static_cast<int>(tl), 64);
       if (keep) {
         const uint64_t p = ((static_cast<uint64_t>(hi) << 32) | lo) + rk;
-        if (p < a.out_cap) a.out_ids[p] = id[u];
+        if (p < a.out_cap) a.out_ids[p] = E::id(e[u]);
       }
       next += static_cast<uint64_t>(__popcll(mine));
     }
@@ -1700,7 +1764,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void small_batch_kernel(SmallArgs
   if (!(flags & (SUM_F_RETRY | SUM_F_ERROR))) {
     if (wv < ntiles) {
       const uint64_t t = uint64_t(wv) * tt + lane;
-      scatter_tile(a, wv, (lane < tt && t < n) ? a.out_off[t] : 0);
+      scatter_tile<SlabWide>(a, wv, (lane < tt && t < n) ? a.out_off[t] : 0);
     }
     const uint32_t fill = min(ctrl(CTRL_DEEP_FILL), a.deep_slab_cap);
     for (uint32_t i = tid; i < fill; i += NT) {
@@ -1876,13 +1940,18 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void small_batch_kernel(SmallArgs
 // ------------------------------------------------------------------------------------
 template <int W, int S, int WC, int K, bool RL = false, bool NH = true>
 static void launch_fast_t(const MatchArgs& a, uint64_t ntiles, hipStream_t s) {
-  const uint64_t grid = (ntiles + W - 1) / W;
-  if (a.diag)
-    hipLaunchKernelGGL((match_fast_kernel<W, S, WC, K, true, RL, 0, NH>), dim3(static_cast<uint32_t>(grid)),
-                       dim3(W * 64), 0, s, a);
-  else
-    hipLaunchKernelGGL((match_fast_kernel<W, S, WC, K, false, RL, 0, NH>), dim3(static_cast<uint32_t>(grid)),
-                       dim3(W * 64), 0, s, a);
+  const dim3 grid(static_cast<uint32_t>((ntiles + W - 1) / W)), block(W * 64);
+  if (a.narrow) {
+    if (a.diag)
+      hipLaunchKernelGGL((match_fast_kernel<W, S, WC, K, true, RL, 0, NH, SlabNarrow>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((match_fast_kernel<W, S, WC, K, false, RL, 0, NH, SlabNarrow>), grid, block, 0, s, a);
+  } else {
+    if (a.diag)
+      hipLaunchKernelGGL((match_fast_kernel<W, S, WC, K, true, RL, 0, NH, SlabWide>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((match_fast_kernel<W, S, WC, K, false, RL, 0, NH, SlabWide>), grid, block, 0, s, a);
+  }
 }
 
 hipError_t launch_match_fast(const MatchArgs& a, FastVariant v, hipStream_t s) {
@@ -1912,8 +1981,11 @@ hipError_t launch_match_fast(const MatchArgs& a, FastVariant v, hipStream_t s) {
         break;
       }
       const dim3 grid(static_cast<uint32_t>((ntiles + 3) / 4));
-      hipLaunchKernelGGL((match_fast_kernel<4, 384, 640, 1, false, false, 1>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((match_fast_kernel<4, 384, 640, 1, false, false, 2>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((match_fast_kernel<4, 384, 640, 1, false, false, 1>), grid, dim3(256), 0, s, a);  // writes no entry
+      if (a.narrow)
+        hipLaunchKernelGGL((match_fast_kernel<4, 384, 640, 1, false, false, 2, true, SlabNarrow>), grid, dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((match_fast_kernel<4, 384, 640, 1, false, false, 2>), grid, dim3(256), 0, s, a);
       break;
     }
     default: return hipErrorInvalidValue;
@@ -1924,7 +1996,7 @@ hipError_t launch_match_fast(const MatchArgs& a, FastVariant v, hipStream_t s) {
 hipError_t launch_small_batch(const SmallArgs& a, hipStream_t s) {
   const uint64_t tiles = a.tt ? (a.m.n + a.tt - 1) / a.tt : 0;
   if (a.m.n == 0 || a.m.n > SMALL_MAX_N || a.tt == 0 || a.tt > TILE_TOPICS || tiles > SMALL_WAVES ||
-      tiles > a.slab_tiles)
+      tiles > a.slab_tiles || a.m.narrow)  // (the kernel writes and reads wide entries)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(small_batch_kernel, dim3(1), dim3(SMALL_WAVES * 64), 0, s, a);
   return hipGetLastError();
@@ -1960,7 +2032,11 @@ hipError_t launch_assemble(const MatchArgs& a, hipStream_t s) {
       if (err == hipSuccess) err = launch_scan(a.corig, a.n, a.out_off, a.partials, s);
       if (err != hipSuccess) return err;
     }
-    hipLaunchKernelGGL(scatter_fast_kernel, dim3(static_cast<uint32_t>((ntiles + 3) / 4)), dim3(256), 0, s, a);
+    const dim3 grid(static_cast<uint32_t>((ntiles + 3) / 4));
+    if (a.narrow)
+      hipLaunchKernelGGL(scatter_fast_kernel<SlabNarrow>, grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(scatter_fast_kernel<SlabWide>, grid, dim3(256), 0, s, a);
   }
   hipLaunchKernelGGL(scatter_deep_kernel, dim3(64), dim3(256), 0, s, a);
   hipLaunchKernelGGL(summary_kernel, dim3(1), dim3(64), 0, s, a);
