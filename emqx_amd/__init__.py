@@ -8,6 +8,8 @@ Modules mirror the reference's Erlang modules on the hot path:
   :mod:`emqx_amd.workloads` synthetic subscription tables / topic streams (BASELINE configs)
   :mod:`emqx_amd.deliver` emqx_session ignore_local/3 + enrich_subopts/3 (No Local, granted QoS, RAP, subid
                           per delivery behind the fan-out)
+  :mod:`emqx_amd.select`  emqx_rule_engine get_rules_for_topic/1, emqx_bridge get_matched_bridges/1, emqx_exhook
+                          match_topic_filter/2 (the hook consumers a published topic selects, each once)
   :mod:`emqx_amd.dist`    multi-GPU: replicated tables + data-parallel topic split,
                           filter-sharded tables with broadcast + gather
 """
@@ -16,3 +18,4 @@ __version__ = "0.1.0"
 
 from ._lib import EngineError, MODE_ROUTES, MODE_TRIE, MODE_TRIE_WILDCARD  # noqa: F401
 from .deliver import SubOpts  # noqa: F401,E402  (delivery options behind the fan-out)
+from .select import HookIndex, OwnerTable  # noqa: F401,E402  (hook consumers selected per publish)

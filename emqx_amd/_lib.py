@@ -80,6 +80,12 @@ DELIVER_EXPORTS = (
     "emqx_deliver_enrich_batch_device", "emqx_deliver_enrich_batch_device_async", "emqx_deliver_enrich_host",
     "emqx_subopts_set_tuning", "emqx_subopts_stats_get",
 )
+# Every symbol include/emqx_select.h declares (hook consumers selected per publish).
+SELECT_EXPORTS = (
+    "emqx_owntab_create", "emqx_owntab_destroy", "emqx_owntab_set", "emqx_owntab_enable", "emqx_owntab_remove",
+    "emqx_owntab_commit", "emqx_select_batch", "emqx_select_batch_device", "emqx_select_batch_device_async",
+    "emqx_select_host", "emqx_owntab_set_tuning", "emqx_owntab_stats_get",
+)
 
 NO_GROUP = 0xFFFFFFFF
 SHARD_NONE = 0xFFFFFFFF
@@ -188,6 +194,31 @@ class SubOptsStats(ctypes.Structure):
         ("size", ctypes.c_uint64),
         ("n_entries", ctypes.c_uint64), ("n_slots", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64),
         ("epoch", ctypes.c_uint64), ("max_probe", ctypes.c_uint64),
+        ("last_build_ms", ctypes.c_double), ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class SelectBatch(ctypes.Structure):
+    """struct emqx_select_batch (include/emqx_select.h): the buffers of one select call."""
+    _fields_ = [
+        ("offsets", ctypes.c_void_p), ("filters", ctypes.c_void_p), ("n", ctypes.c_uint64), ("cap_in", ctypes.c_uint64),
+        ("msg_classes", ctypes.c_void_p), ("out_offsets", ctypes.c_void_p), ("out_owners", ctypes.c_void_p),
+        ("cap_out", ctypes.c_uint64),
+    ]
+
+
+class OwnTabStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("n_owners", ctypes.c_uint64), ("n_filters", ctypes.c_uint64), ("n_postings", ctypes.c_uint64),
+        ("n_match_all", ctypes.c_uint64), ("max_list", ctypes.c_uint64), ("epoch", ctypes.c_uint64),
         ("last_build_ms", ctypes.c_double), ("last_call_ms", ctypes.c_double),
     ]
 
@@ -341,6 +372,18 @@ def lib():
         "emqx_deliver_enrich_host": (i32, [vp, ctypes.POINTER(DeliverBatch), ctypes.POINTER(u64), vp]),
         "emqx_subopts_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_subopts_stats_get": (i32, [vp, ctypes.POINTER(SubOptsStats)]),
+        "emqx_owntab_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_owntab_destroy": (i32, [vp]),
+        "emqx_owntab_set": (i32, [vp, u32, u32, u32, vp, u64]),
+        "emqx_owntab_enable": (i32, [vp, vp, u64, ctypes.c_int32]),
+        "emqx_owntab_remove": (i32, [vp, vp, u64]),
+        "emqx_owntab_commit": (i32, [vp]),
+        "emqx_select_batch": (i32, [vp, ctypes.POINTER(SelectBatch), ctypes.POINTER(u64), vp]),
+        "emqx_select_batch_device": (i32, [vp, ctypes.POINTER(SelectBatch), ctypes.POINTER(u64), vp, vp]),
+        "emqx_select_batch_device_async": (i32, [vp, ctypes.POINTER(SelectBatch), vp, vp]),
+        "emqx_select_host": (i32, [vp, ctypes.POINTER(SelectBatch), ctypes.POINTER(u64), vp]),
+        "emqx_owntab_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_owntab_stats_get": (i32, [vp, ctypes.POINTER(OwnTabStats)]),
         "emqx_commit_stats": (i32, [vp, vp, u32]),
         "emqx_shard_owner": (i32, [vp, vp, u64, u32, u32, i32, vp]),
         "emqx_shard_owner_device": (i32, [vp, vp, u64, u32, u32, vp, vp]),
