@@ -222,6 +222,7 @@ struct emqx_engine {
   std::atomic<uint64_t> order_bpt{48};  // reordered-batch bytes per topic to provision (learnt)
   std::atomic<double> last_order_ms{0};
   std::atomic<bool> small_batch{true};  // emqx_set_tuning("small_batch", 0|1): the one-launch path
+  std::atomic<int> scatter_stage{-1};   // emqx_set_tuning("scatter_stage", -1 auto | 0 direct | 1 staged)
 };
 
 namespace {
@@ -544,6 +545,23 @@ FastVariant pick_variant(const emqx_engine* e, const Snapshot& snap) {
   return snap.max_depth > 12 ? FAST_K1_S512W : FAST_K1_S384B1;
 }
 
+// The CSR scatter of batch-order calls: staged through LDS (match_kernels.hip
+// scatter_tile_staged) or direct.  emqx_set_tuning("scatter_stage") decides, else
+// EMQX_SCATTER_STAGE=0|1 (A/B runs of one build), else the table and the workspace: staged for
+// the shallow tables the one-wave walk variant serves, once some tile has needed more than the
+// initial slab of 256 entries.  A workspace still at 256 (config A: ~50 ids a tile, two or three
+// output lines) has nothing to merge, and the staged kernel's one-wave launch costs it 0.7 %.
+bool use_scatter_stage(const emqx_engine* e, const Snapshot& snap, uint32_t slab_per_tile) {
+  static const int env_forced = [] {
+    const char* v = getenv("EMQX_SCATTER_STAGE");
+    return v ? atoi(v) : -1;
+  }();
+  const int tv = e->scatter_stage.load();
+  const int forced = tv >= 0 ? tv : env_forced;
+  if (forced >= 0) return forced != 0;
+  return snap.max_depth <= 12 && slab_per_tile > 256;
+}
+
 // Enqueue one match call on stream s (no host synchronisation): memset of the control
 // words, fast kernel, deep kernel, tile scan (+ summary into `summary`), scatter.  A call on
 // a workspace last used from another stream first waits for that call to drain.
@@ -585,6 +603,7 @@ MatchArgs match_args(emqx_engine* e, const Snapshot& snap, Workspace* w, uint32_
   a.out_off = d_out_off;
   a.out_ids = d_out_ids;
   a.out_cap = d_out_ids ? cap : 0;
+  a.scatter_stage = use_scatter_stage(e, snap, a.slab_cap) ? 1u : 0u;
   a.summary = summary;
   return a;
 }
@@ -1382,6 +1401,11 @@ int emqx_set_tuning(emqx_engine* e, const char* key, int64_t value) {
   if (std::strcmp(key, "order") == 0) {
     if (value < -1 || value > 1) return EMQX_EINVAL;
     e->order.store(static_cast<int>(value));
+    return EMQX_OK;
+  }
+  if (std::strcmp(key, "scatter_stage") == 0) {
+    if (value < -1 || value > 1) return EMQX_EINVAL;
+    e->scatter_stage.store(static_cast<int>(value));
     return EMQX_OK;
   }
   if (std::strcmp(key, "order_level_bits") == 0) {

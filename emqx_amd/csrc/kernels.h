@@ -25,6 +25,11 @@ constexpr uint32_t CTRL_ERR_ORDER_CAP = 8u;  // walk order: the reordered topic 
 
 constexpr int TILE_TOPICS = 64;
 
+// Staged CSR scatter (match_kernels.hip scatter_tile_staged): ids per LDS window of a wave, and
+// the windows a tile may take; a tile with more ids is scattered directly.
+constexpr uint32_t SCATTER_STAGE_W = 1024;
+constexpr uint32_t SCATTER_STAGE_P = 8;
+
 // Diagnostic counters (emqx_set_tuning("diag", 1); read with emqx_diag_read).
 enum Diag : uint32_t {
   DIAG_STEPS = 0,        // frontier steps (wave iterations)
@@ -103,6 +108,7 @@ struct MatchArgs {
   uint64_t* out_off;       // [n + 1] CSR offsets (caller's)
   uint32_t* out_ids;       // [out_cap] CSR ids (caller's)
   uint64_t out_cap;
+  uint32_t scatter_stage;  // 1: tiles that allow it go through the LDS window (SCATTER_STAGE_*)
   uint64_t* summary;       // [SUM_WORDS] (device or host-pinned memory)
   // walk order (order_kernels.hip): the batch is walked in prefix-key order
   const uint32_t* perm;    // [n] batch position -> caller's topic index (nullptr: identity);

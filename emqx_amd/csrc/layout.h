@@ -105,6 +105,22 @@ struct SlabNarrow {
   static EMQX_HD uint32_t id(T e) { return e & ((1u << SLAB_NARROW_ID_BITS) - 1u); }
 };
 
+// A span of `len` 4-byte entries starting at byte address `addr` (a multiple of 4), cut for
+// 16-byte stores (the staged CSR scatter's copy-out): `head` single entries up to the first
+// 16-byte boundary, `vecs` aligned 16-byte vectors, `tail` single entries (< 4).  A span that
+// holds no whole aligned vector comes back with vecs = 0.  head + 4 * vecs + tail == len always.
+struct SpanSplit {
+  uint32_t head, vecs, tail;
+};
+EMQX_HD SpanSplit span_split(uint64_t addr, uint32_t len) {
+  const uint32_t to_boundary = static_cast<uint32_t>((16u - (addr & 15u)) & 15u) >> 2;
+  SpanSplit s;
+  s.head = to_boundary < len ? to_boundary : len;
+  s.vecs = (len - s.head) >> 2;
+  s.tail = len - s.head - 4u * s.vecs;
+  return s;
+}
+
 // One in-place rewrite of an existing slot by an incremental commit (live_trie.cpp): the
 // slot's new content and its two filter ids.
 struct alignas(16) SlotPatch {

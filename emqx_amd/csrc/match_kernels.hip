@@ -1469,6 +1469,25 @@ __global__ __launch_bounds__(GROUP_TILES) void group_reduce_kernel(MatchArgs a, 
 // advance every topic's running position — no atomics.  Ids beyond out_cap are dropped.
 template <class E>
 __device__ __forceinline__ void scatter_tile(const MatchArgs& a, uint64_t tile, uint64_t off);
+template <class E>
+__device__ __forceinline__ void scatter_tile_staged(const MatchArgs& a, uint64_t tile, uint64_t base, uint32_t rel,
+                                                    uint32_t tsum, uint32_t* win);
+
+// The output position of this lane's topic of `tile` in batch order (every lane of a tile's
+// wave gets one: lanes past the batch's end the position behind its last topic), written to
+// out_off.
+__device__ __forceinline__ uint64_t tile_offsets(const MatchArgs& a, uint64_t tile, uint32_t lane) {
+  const uint64_t t = tile * TILE_TOPICS + lane;
+  const uint64_t g = tile / GROUP_TILES, g0 = g * GROUP_TILES;
+  uint64_t before = 0;
+  for (uint64_t k = lane; k < g; k += 64) before += a.group_sum[k];
+  for (uint64_t j = g0 + lane; j < tile; j += 64) before += a.tile_sum[j];
+  before = wave_sum64(before);
+  const uint64_t c = t < a.n ? a.counts[t] : 0;
+  const uint64_t off = before + wave_incl_scan64(c, lane) - c;
+  if (t < a.n) a.out_off[t] = off;
+  return off;
+}
 
 template <class E>
 __global__ __launch_bounds__(256) void scatter_fast_kernel(MatchArgs a) {
@@ -1483,16 +1502,46 @@ __global__ __launch_bounds__(256) void scatter_fast_kernel(MatchArgs a) {
     if (a.ctrl[CTRL_ERROR] & CTRL_ERR_ORDER_CAP) return;
     off = t < a.n ? a.out_off[a.perm[t]] : 0;
   } else {
-    const uint64_t g = tile / GROUP_TILES, g0 = g * GROUP_TILES;
-    uint64_t before = 0;
-    for (uint64_t k = lane; k < g; k += 64) before += a.group_sum[k];
-    for (uint64_t j = g0 + lane; j < tile; j += 64) before += a.tile_sum[j];
-    before = wave_sum64(before);
-    const uint64_t c = t < a.n ? a.counts[t] : 0;
-    off = before + wave_incl_scan64(c, lane) - c;
-    if (t < a.n) a.out_off[t] = off;
+    off = tile_offsets(a, tile, lane);
   }
   scatter_tile<E>(a, tile, off);
+}
+
+// The staged scatter (batch order only; MatchArgs::scatter_stage): one wave per block, so its
+// window fits the LDS a resident walk leaves free on the CU.  A tile whose ids form one
+// contiguous, complete span of out_ids — nothing deferred, no slab overflow, within out_cap —
+// of at most SCATTER_STAGE_P windows goes through the window; any other takes scatter_tile.
+template <class E>
+__global__ __launch_bounds__(64) void scatter_staged_kernel(MatchArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t win[SCATTER_STAGE_W + 4];
+  const uint32_t lane = lane_id();
+  const uint64_t tile = blockIdx.x;
+  const uint64_t off = tile_offsets(a, tile, lane);
+  const uint64_t base = (static_cast<uint64_t>(__shfl(static_cast<uint32_t>(off >> 32), 0, 64)) << 32) |
+                        __shfl(static_cast<uint32_t>(off), 0, 64);
+  const uint64_t tsum = a.tile_sum[tile];
+  const bool staged = a.tile_defer[tile] == 0 && a.tile_fill[tile] <= a.slab_cap &&
+                      tsum <= static_cast<uint64_t>(SCATTER_STAGE_P) * SCATTER_STAGE_W && base + tsum <= a.out_cap;
+  if (staged)  // wave-uniform
+    scatter_tile_staged<E>(a, tile, base, static_cast<uint32_t>(off - base), static_cast<uint32_t>(tsum), win);
+  else
+    scatter_tile<E>(a, tile, off);
+}
+
+// One round of 64 slab entries: lanes holding the same topic find each other with six ballots
+// (one per bit of the topic index).  Returns this lane's entry's rank among the round's kept
+// entries of its topic tl; *cnt = the round's kept entries of topic `lane`.
+__device__ __forceinline__ uint32_t round_ranks(bool keep, uint32_t tl, uint32_t lane, uint64_t lt, uint32_t* cnt) {
+  const uint64_t km = __ballot(keep);
+  uint64_t peers = km, mine = km;
+#pragma unroll
+  for (uint32_t bit = 0; bit < 6; ++bit) {
+    const uint64_t m = __ballot(keep && ((tl >> bit) & 1u));
+    peers &= ((tl >> bit) & 1u) ? m : ~m;
+    mine &= ((lane >> bit) & 1u) ? m : ~m;
+  }
+  *cnt = static_cast<uint32_t>(__popcll(mine));
+  return static_cast<uint32_t>(__popcll(peers & lt));
 }
 
 // Lane L keeps topic L's next output position in a register.  Per round of 64 entries the
@@ -1524,23 +1573,73 @@ __device__ __forceinline__ void scatter_tile(const MatchArgs& a, uint64_t tile, 
       if (i0 + 64 * u >= fill) break;  // wave-uniform: the rounds past the tile's last entry
       const uint32_t tl = E::owner(e[u]);
       const bool keep = e[u] != E::PAD && !((dmask >> tl) & 1ull);
-      const uint64_t km = __ballot(keep);
-      uint64_t peers = km, mine = km;
-#pragma unroll
-      for (uint32_t bit = 0; bit < 6; ++bit) {
-        const uint64_t m = __ballot(keep && ((tl >> bit) & 1u));
-        peers &= ((tl >> bit) & 1u) ? m : ~m;
-        mine &= ((lane >> bit) & 1u) ? m : ~m;
-      }
-      const uint32_t rk = static_cast<uint32_t>(__popcll(peers & lt));
+      uint32_t cnt;
+      const uint32_t rk = round_ranks(keep, tl, lane, lt, &cnt);
       const uint32_t lo = __shfl(static_cast<uint32_t>(next), static_cast<int>(tl), 64);
       const uint32_t hi = __shfl(static_cast<uint32_t>(next >> 32), static_cast<int>(tl), 64);
       if (keep) {
         const uint64_t p = ((static_cast<uint64_t>(hi) << 32) | lo) + rk;
         if (p < a.out_cap) a.out_ids[p] = E::id(e[u]);
       }
-      next += static_cast<uint64_t>(__popcll(mine));
+      next += cnt;
     }
+  }
+}
+
+// scatter_tile through an LDS window, for a tile whose ids fill out_ids[base, base + tsum)
+// completely and whose slab holds no entry to skip.  A wave's direct stores of one round land
+// in most of the span's 64-B lines, a partial write each; here pass k walks the tile's slab
+// again (L1 / L2 hits), with the same ranks and running positions — relative to base, in 32
+// bits, so one cross-lane read each — and keeps the ids of positions [kW, (k + 1)W) in the
+// window, which then leaves in aligned 16-byte stores (layout.h span_split on the real
+// address: out_ids is only 4-byte aligned in general).  The window is shifted by the span's
+// misalignment, so its vector reads are aligned too.  No store leaves the tile's span.
+// rel: this lane's topic's first position minus base.  win: SCATTER_STAGE_W + 4 entries.
+template <class E>
+__device__ __forceinline__ void scatter_tile_staged(const MatchArgs& a, uint64_t tile, uint64_t base, uint32_t rel,
+                                                    uint32_t tsum, uint32_t* win) {
+  typedef typename E::T T;
+  constexpr uint32_t W = SCATTER_STAGE_W;
+  const uint32_t lane = lane_id();
+  const uint32_t fill = a.tile_fill[tile];
+  const T* slab = static_cast<const T*>(a.slab) + tile * a.slab_cap;
+  const uint64_t lt = lanemask_lt(lane);
+  constexpr uint32_t U = 32 / sizeof(T);
+  for (uint32_t w0 = 0; w0 < tsum; w0 += W) {
+    uint32_t* dst = a.out_ids + base + w0;
+    const uint32_t len = min(W, tsum - w0);
+    const uint64_t addr = reinterpret_cast<uint64_t>(dst);
+    const uint32_t mis = static_cast<uint32_t>(addr >> 2) & 3u;  // window slot of dst[0]
+    uint32_t next = rel;
+    for (uint32_t i0 = 0; i0 < fill; i0 += 64 * U) {
+      T e[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) {
+        const uint32_t i = i0 + 64 * u + lane;
+        e[u] = i < fill ? slab[i] : E::PAD;
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) {
+        if (i0 + 64 * u >= fill) break;  // wave-uniform
+        const uint32_t tl = E::owner(e[u]);
+        const bool keep = e[u] != E::PAD;
+        uint32_t cnt;
+        const uint32_t rk = round_ranks(keep, tl, lane, lt, &cnt);
+        const uint32_t d = __shfl(next, static_cast<int>(tl), 64) + rk - w0;  // (wraps below the window)
+        if (keep && d < len) win[mis + d] = E::id(e[u]);
+        next += cnt;
+      }
+    }
+    wave_sync();
+    const SpanSplit sp = span_split(addr, len);
+    if (lane < sp.head) dst[lane] = win[mis + lane];
+    for (uint32_t v = lane; v < sp.vecs; v += 64) {
+      const uint32_t i = sp.head + 4 * v;  // mis + head is a multiple of 4 whenever vecs > 0
+      *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<const uint4*>(win + mis + i);
+    }
+    const uint32_t t0 = sp.head + 4 * sp.vecs;
+    if (lane < sp.tail) dst[t0 + lane] = win[mis + t0 + lane];
+    wave_sync();  // the next pass overwrites the window
   }
 }
 
@@ -2033,7 +2132,13 @@ hipError_t launch_assemble(const MatchArgs& a, hipStream_t s) {
       if (err != hipSuccess) return err;
     }
     const dim3 grid(static_cast<uint32_t>((ntiles + 3) / 4));
-    if (a.narrow)
+    if (a.scatter_stage && !a.perm) {  // (a reordered batch's tiles have no contiguous span)
+      const dim3 tiles(static_cast<uint32_t>(ntiles));
+      if (a.narrow)
+        hipLaunchKernelGGL(scatter_staged_kernel<SlabNarrow>, tiles, dim3(64), 0, s, a);
+      else
+        hipLaunchKernelGGL(scatter_staged_kernel<SlabWide>, tiles, dim3(64), 0, s, a);
+    } else if (a.narrow)
       hipLaunchKernelGGL(scatter_fast_kernel<SlabNarrow>, grid, dim3(256), 0, s, a);
     else
       hipLaunchKernelGGL(scatter_fast_kernel<SlabWide>, grid, dim3(256), 0, s, a);

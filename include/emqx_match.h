@@ -623,7 +623,11 @@ int emqx_topic_wildcard(const uint8_t* topic, uint64_t len);
  * incremental commit, default min(8, cores)), "timeline" (tiles of emqx_diag_timeline to record,
  * 0 = off), "small_batch" (1 = default: host / publish batches of at most 1024 topics run as one
  * kernel launch that reads the pinned inputs and writes the pinned outputs itself; 0 = the
- * batched pipeline).  EMQX_ENOTFOUND for unknown keys. */
+ * batched pipeline), "scatter_stage" (how batch-order calls write out_ids: 1 = tiles that allow
+ * it are staged through LDS and stored in 16-byte vectors, 0 = every id stored on its own,
+ * -1 = default: staged on tables up to 12 levels deep once a tile has needed more than the
+ * initial 256 slab entries; the CSR is the same either way).
+ * EMQX_ENOTFOUND for unknown keys. */
 int emqx_set_tuning(emqx_engine* e, const char* key, int64_t value);
 /* Reads (and optionally resets) the accumulated diagnostic counters (DIAG_* order). */
 int emqx_diag_read(emqx_engine* e, uint64_t* out, uint32_t n, int reset);
