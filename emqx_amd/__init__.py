@@ -10,6 +10,8 @@ Modules mirror the reference's Erlang modules on the hot path:
                           per delivery behind the fan-out)
   :mod:`emqx_amd.select`  emqx_rule_engine get_rules_for_topic/1, emqx_bridge get_matched_bridges/1, emqx_exhook
                           match_topic_filter/2 (the hook consumers a published topic selects, each once)
+  :mod:`emqx_amd.inbox`   emqx_connection's drain of {deliver, ...} into emqx_channel:handle_deliver/2's list (a
+                          batch's deliveries grouped by subscriber, in batch order)
   :mod:`emqx_amd.dist`    multi-GPU: replicated tables + data-parallel topic split,
                           filter-sharded tables with broadcast + gather
 """
@@ -19,3 +21,4 @@ __version__ = "0.1.0"
 from ._lib import EngineError, MODE_ROUTES, MODE_TRIE, MODE_TRIE_WILDCARD  # noqa: F401
 from .deliver import SubOpts  # noqa: F401,E402  (delivery options behind the fan-out)
 from .select import HookIndex, OwnerTable  # noqa: F401,E402  (hook consumers selected per publish)
+from .inbox import Inbox  # noqa: F401,E402  (a batch's deliveries grouped by subscriber)

@@ -86,6 +86,12 @@ SELECT_EXPORTS = (
     "emqx_owntab_commit", "emqx_select_batch", "emqx_select_batch_device", "emqx_select_batch_device_async",
     "emqx_select_host", "emqx_owntab_set_tuning", "emqx_owntab_stats_get",
 )
+# Every symbol include/emqx_inbox.h declares (a batch's deliveries grouped by subscriber).
+INBOX_EXPORTS = (
+    "emqx_inbox_create", "emqx_inbox_destroy", "emqx_inbox_reserve", "emqx_inbox_group_batch",
+    "emqx_inbox_group_batch_device", "emqx_inbox_group_batch_device_async", "emqx_inbox_group_host",
+    "emqx_inbox_set_tuning", "emqx_inbox_stats_get",
+)
 
 NO_GROUP = 0xFFFFFFFF
 SHARD_NONE = 0xFFFFFFFF
@@ -220,6 +226,34 @@ class OwnTabStats(ctypes.Structure):
         ("n_owners", ctypes.c_uint64), ("n_filters", ctypes.c_uint64), ("n_postings", ctypes.c_uint64),
         ("n_match_all", ctypes.c_uint64), ("max_list", ctypes.c_uint64), ("epoch", ctypes.c_uint64),
         ("last_build_ms", ctypes.c_double), ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class InboxBatch(ctypes.Structure):
+    """struct emqx_inbox_batch (include/emqx_inbox.h): the buffers of one group call."""
+    _fields_ = [
+        ("offsets", ctypes.c_void_p), ("subs", ctypes.c_void_p), ("filters", ctypes.c_void_p),
+        ("opts", ctypes.c_void_p), ("subids", ctypes.c_void_p),
+        ("n", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("sub_limit", ctypes.c_uint64),
+        ("box_msgs", ctypes.c_void_p), ("box_filters", ctypes.c_void_p), ("box_opts", ctypes.c_void_p),
+        ("box_subids", ctypes.c_void_p), ("box_src", ctypes.c_void_p),
+        ("inbox_subs", ctypes.c_void_p), ("inbox_offsets", ctypes.c_void_p), ("cap_boxes", ctypes.c_uint64),
+    ]
+
+
+class InboxStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_in", ctypes.c_uint64), ("sub_limit", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64),
+        ("path", ctypes.c_uint64), ("calls", ctypes.c_uint64), ("last_passes", ctypes.c_uint64),
+        ("last_call_ms", ctypes.c_double),
     ]
 
     def __init__(self, *a, **kw):
@@ -384,6 +418,15 @@ def lib():
         "emqx_select_host": (i32, [vp, ctypes.POINTER(SelectBatch), ctypes.POINTER(u64), vp]),
         "emqx_owntab_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_owntab_stats_get": (i32, [vp, ctypes.POINTER(OwnTabStats)]),
+        "emqx_inbox_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_inbox_destroy": (i32, [vp]),
+        "emqx_inbox_reserve": (i32, [vp, u64, u64]),
+        "emqx_inbox_group_batch": (i32, [vp, ctypes.POINTER(InboxBatch), ctypes.POINTER(u64), vp]),
+        "emqx_inbox_group_batch_device": (i32, [vp, ctypes.POINTER(InboxBatch), ctypes.POINTER(u64), vp, vp]),
+        "emqx_inbox_group_batch_device_async": (i32, [vp, ctypes.POINTER(InboxBatch), vp, vp]),
+        "emqx_inbox_group_host": (i32, [vp, ctypes.POINTER(InboxBatch), ctypes.POINTER(u64), vp]),
+        "emqx_inbox_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_inbox_stats_get": (i32, [vp, ctypes.POINTER(InboxStats)]),
         "emqx_commit_stats": (i32, [vp, vp, u32]),
         "emqx_shard_owner": (i32, [vp, vp, u64, u32, u32, i32, vp]),
         "emqx_shard_owner_device": (i32, [vp, vp, u64, u32, u32, vp, vp]),
