@@ -12,6 +12,8 @@ Modules mirror the reference's Erlang modules on the hot path:
                           match_topic_filter/2 (the hook consumers a published topic selects, each once)
   :mod:`emqx_amd.inbox`   emqx_connection's drain of {deliver, ...} into emqx_channel:handle_deliver/2's list (a
                           batch's deliveries grouped by subscriber, in batch order)
+  :mod:`emqx_amd.window`  emqx_session deliver/2 + enqueue/2, emqx_inflight is_full/1, emqx_mqueue in/2 (inflight and
+                          mqueue admission of every inbox: packet ids, what is queued, what is dropped)
   :mod:`emqx_amd.dist`    multi-GPU: replicated tables + data-parallel topic split,
                           filter-sharded tables with broadcast + gather
 """
@@ -22,3 +24,4 @@ from ._lib import EngineError, MODE_ROUTES, MODE_TRIE, MODE_TRIE_WILDCARD  # noq
 from .deliver import SubOpts  # noqa: F401,E402  (delivery options behind the fan-out)
 from .select import HookIndex, OwnerTable  # noqa: F401,E402  (hook consumers selected per publish)
 from .inbox import Inbox  # noqa: F401,E402  (a batch's deliveries grouped by subscriber)
+from .window import Window  # noqa: F401,E402  (inflight and mqueue admission per inbox)

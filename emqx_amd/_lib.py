@@ -92,6 +92,12 @@ INBOX_EXPORTS = (
     "emqx_inbox_group_batch_device", "emqx_inbox_group_batch_device_async", "emqx_inbox_group_host",
     "emqx_inbox_set_tuning", "emqx_inbox_stats_get",
 )
+# Every symbol include/emqx_window.h declares (inflight and mqueue admission per inbox).
+WINDOW_EXPORTS = (
+    "emqx_window_create", "emqx_window_destroy", "emqx_window_reserve", "emqx_window_run_batch",
+    "emqx_window_run_batch_device", "emqx_window_run_batch_device_async", "emqx_window_run_host",
+    "emqx_window_set_tuning", "emqx_window_stats_get",
+)
 
 NO_GROUP = 0xFFFFFFFF
 SHARD_NONE = 0xFFFFFFFF
@@ -254,6 +260,33 @@ class InboxStats(ctypes.Structure):
         ("cap_in", ctypes.c_uint64), ("sub_limit", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64),
         ("path", ctypes.c_uint64), ("calls", ctypes.c_uint64), ("last_passes", ctypes.c_uint64),
         ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class WindowBatch(ctypes.Structure):
+    """struct emqx_window_batch (include/emqx_window.h): the buffers of one call."""
+    _fields_ = [
+        ("inbox_subs", ctypes.c_void_p), ("inbox_offsets", ctypes.c_void_p), ("box_opts", ctypes.c_void_p),
+        ("n_boxes", ctypes.c_void_p),
+        ("m", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("update_table", ctypes.c_uint64),
+        ("verdicts", ctypes.c_void_p), ("pkt_ids", ctypes.c_void_p), ("out_sessions", ctypes.c_void_p),
+        ("out_counts", ctypes.c_void_p),
+    ]
+
+
+class WindowStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64),
+        ("path", ctypes.c_uint64), ("calls", ctypes.c_uint64), ("last_call_ms", ctypes.c_double),
     ]
 
     def __init__(self, *a, **kw):
@@ -427,6 +460,15 @@ def lib():
         "emqx_inbox_group_host": (i32, [vp, ctypes.POINTER(InboxBatch), ctypes.POINTER(u64), vp]),
         "emqx_inbox_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_inbox_stats_get": (i32, [vp, ctypes.POINTER(InboxStats)]),
+        "emqx_window_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_window_destroy": (i32, [vp]),
+        "emqx_window_reserve": (i32, [vp, u64, u64]),
+        "emqx_window_run_batch": (i32, [vp, ctypes.POINTER(WindowBatch), vp]),
+        "emqx_window_run_batch_device": (i32, [vp, ctypes.POINTER(WindowBatch), vp, vp]),
+        "emqx_window_run_batch_device_async": (i32, [vp, ctypes.POINTER(WindowBatch), vp, vp]),
+        "emqx_window_run_host": (i32, [vp, ctypes.POINTER(WindowBatch), vp]),
+        "emqx_window_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_window_stats_get": (i32, [vp, ctypes.POINTER(WindowStats)]),
         "emqx_commit_stats": (i32, [vp, vp, u32]),
         "emqx_shard_owner": (i32, [vp, vp, u64, u32, u32, i32, vp]),
         "emqx_shard_owner_device": (i32, [vp, vp, u64, u32, u32, vp, vp]),

@@ -29,8 +29,8 @@
  * order in which one publisher's sends would have reached the mailbox.  The result is a pure
  * function of the input: two runs are byte-identical.
  *
- * Kept by the caller: the pid lookup and the send, active_n slicing of an inbox, inflight and
- * mqueue.
+ * Kept by the caller: the pid lookup and the send, active_n slicing of an inbox.  Inflight and
+ * mqueue admission of every inbox is the next stage (emqx_window.h).
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.
  *

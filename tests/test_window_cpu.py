@@ -1,0 +1,330 @@
+"""CPU-side checks of the window stage (include/emqx_window.h) on a host-only handle: the
+restatement (tests/window_ref.py) against the known answers of the reference's own suites
+(tests/golden/window_kats.json), emqx_window_run_host against the restatement on every case, the
+exports, the argument errors, and no batch call without a device."""
+
+import ctypes
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import window_cases as C
+from tests import window_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL, EDEVICE, EOVERFLOW, ENOTFOUND = -1, -3, -4, -5
+KATS = json.load(open(os.path.join(ROOT, "tests", "golden", "window_kats.json")))["kats"]
+
+
+@pytest.fixture(scope="module")
+def W():
+    lib_path = os.path.join(ROOT, "emqx_amd", "_build", "libemqxmatch.so")
+    if not os.path.exists(lib_path):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "emqx_amd", "csrc"), "-j4"], check=True,
+                       capture_output=True)
+    from emqx_amd import window
+    return window
+
+
+def host(W):
+    return W.Window(W.HOST_ONLY)
+
+
+def run(W, case, **kw):
+    """The host evaluator on a copy of the case's table; a bad subscriber's EINVAL carries the outputs."""
+    from emqx_amd import _lib
+    table = case.table.copy()
+    try:
+        got = host(W).run_host(case.subs, case.offsets, case.opts, table, **kw)
+        assert not case.reference()["summary"][0]
+    except _lib.EngineError as e:
+        assert e.code == EINVAL and e.summary["flags"] == R.F_BAD_SUB
+        got = e.partial
+    return got, table
+
+
+# ---- the restatement against the reference's suites ---------------------------------------------
+
+@pytest.mark.parametrize("kat", KATS, ids=[k["name"] for k in KATS])
+def test_ref_against_the_reference_suites(kat):
+    assert re.fullmatch(r"emqx_(mqueue|inflight|session)_SUITE:t_\w+", kat["source"])
+    verdicts, ids, after, counts, drops, reused = R.session_fold(kat["session"], kat["opts"])
+    assert verdicts == kat["verdicts"] and ids == kat["pkt_ids"]
+    assert {f: after[f] for f in kat["after"]} == kat["after"]
+    assert counts == kat["counts"] and drops == kat["drops"] and not reused
+
+
+def test_kats_cover_the_named_suite_tests():
+    want = {"emqx_mqueue_SUITE:t_in", "emqx_mqueue_SUITE:t_in_qos0", "emqx_mqueue_SUITE:t_simple_mqueue",
+            "emqx_mqueue_SUITE:t_infinity_simple_mqueue", "emqx_mqueue_SUITE:t_dropped", "emqx_inflight_SUITE:t_is_full",
+            "emqx_session_SUITE:t_deliver_qos0", "emqx_session_SUITE:t_deliver_qos1", "emqx_session_SUITE:t_deliver_qos2",
+            "emqx_session_SUITE:t_deliver_when_inflight_is_full", "emqx_session_SUITE:t_enqueue",
+            "emqx_session_SUITE:t_next_pakt_id"}
+    assert {k["source"] for k in KATS} == want
+
+
+@pytest.mark.parametrize("kat", KATS, ids=[k["name"] for k in KATS])
+def test_host_against_the_reference_suites(W, kat):
+    table = C.table_of([kat["session"]])
+    got = host(W).run_host([0], [0, len(kat["opts"])], kat["opts"], table)
+    assert got.verdicts.tolist() == kat["verdicts"] and got.pkt_ids.tolist() == kat["pkt_ids"]
+    assert {f: int(got.out_sessions[f][0]) for f in kat["after"]} == kat["after"]
+    assert got.counts[0].tolist() == kat["counts"] and got.summary["drops"] == kat["drops"]
+
+
+# ---- the ABI ------------------------------------------------------------------------------------
+
+def test_exports_every_window_symbol(W):
+    from emqx_amd import _lib
+    from tests.test_abi_cpu import header_functions
+    declared = header_functions("emqx_window.h")
+    assert len(declared) == 9
+    assert sorted(_lib.WINDOW_EXPORTS) == declared
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
+    for name in declared:
+        assert hasattr(_lib.lib(), name), name
+        assert re.search(r"\bT %s\b" % name, nm), name
+
+
+def test_package_exports_the_module(W):
+    import emqx_amd
+    assert emqx_amd.Window is W.Window
+
+
+def test_constants_mirror_the_headers(W):
+    src = open(os.path.join(ROOT, "emqx_amd", "csrc", "window.h")).read()
+    block = int(re.search(r"WN_BLOCK = (\d+);", src).group(1))
+    rows = int(re.search(r"WN_ROWS = (\d+);", src).group(1))
+    assert re.search(r"WN_TILE = WN_BLOCK \* WN_ROWS;", src)
+    assert (W.BLOCK, W.ROWS, W.TILE) == (block, rows, block * rows) and C.T == W.TILE
+    pub = open(os.path.join(ROOT, "include", "emqx_window.h")).read()
+    for name in ("W_SEND_QOS0", "W_SEND", "W_QUEUED", "W_QUEUED_DROPPED", "W_DROP_QOS0", "W_SKIP_NO_LOCAL", "W_BAD_MESSAGE",
+                 "W_NO_SESSION", "W_PASS", "W_EVICTS"):
+        value = int(re.search(r"#define EMQX_%s (\w+?)u?\b" % name, pub).group(1), 0)
+        assert value == getattr(W, name) == getattr(R, name), name
+    for name in ("PRESENT", "CONNECTED", "STORE_QOS0", "PASS", "F_INPUT_REFUSED", "F_BAD_SUB", "SUMMARY_WORDS"):
+        value = int(re.search(r"#define EMQX_WINDOW_%s (\w+?)u?\b" % name, pub).group(1), 0)
+        assert value == getattr(W, name), name
+        assert name == "SUMMARY_WORDS" or value == getattr(R, name)
+    dl = open(os.path.join(ROOT, "include", "emqx_deliver.h")).read()
+    for name, value in (("QOS_MASK", R.QOS_MASK), ("DROP_NO_LOCAL", R.DROP_NO_LOCAL), ("BAD_MESSAGE", R.BAD_MESSAGE)):
+        assert int(re.search(r"#define EMQX_DELIVER_%s (\w+?)u?\b" % name, dl).group(1), 0) == value
+    assert W.SESSION.itemsize == 32 and W.SESSION.names == R.FIELDS and len(W.SUMMARY) == 8
+
+
+def test_pack_sessions(W):
+    t = W.pack_sessions(3, inflight=[1, 2, 3], flags=W.PRESENT, dropped=1 << 40)
+    assert t.dtype == W.SESSION and t["inflight"].tolist() == [1, 2, 3] and t["inflight_max"].tolist() == [32] * 3
+    assert t["mq_max"].tolist() == [1000] * 3 and t["flags"].tolist() == [1] * 3 and int(t["dropped"][2]) == 1 << 40
+    assert t.tobytes()[:32] == np.array([1, 32, 0, 1000, 1, 1, 0, 256], dtype="<u4").tobytes()
+
+
+def test_batch_calls_need_a_device(W):
+    from emqx_amd import _lib
+    h = host(W)
+    case = C.edge("free_window_0")
+    with pytest.raises(_lib.EngineError) as e:
+        h.run(case.subs, case.offsets, case.opts, case.table.copy())
+    assert e.value.code == EDEVICE
+    b = W.Window.batch(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    with pytest.raises(_lib.EngineError) as e:
+        h.run_device(b)
+    assert e.value.code == EDEVICE
+    with pytest.raises(_lib.EngineError) as e:
+        h.run_device_async(b, 0)
+    assert e.value.code == EDEVICE
+    with pytest.raises(_lib.EngineError) as e:
+        h.reserve(1000, 1000)
+    assert e.value.code == EDEVICE
+
+
+# ---- the host evaluator against the restatement -------------------------------------------------
+
+@pytest.mark.parametrize("name", list(C.LAYOUTS))
+def test_layouts(W, name):
+    case = C.LAYOUTS[name]()
+    got, table = run(W, case)
+    C.check(case.reference(), got)
+    assert table.tobytes() == case.table.tobytes()  # update_table = 0: the table is untouched
+
+
+@pytest.mark.parametrize("name", list(C.EDGES))
+def test_edges(W, name):
+    case = C.edge(name)
+    got, _ = run(W, case)
+    C.check(case.reference(), got)
+
+
+def test_edges_mean_what_their_names_say():
+    """The edge cases are the ones the contract names: read off the restatement's answer."""
+    def box(name):
+        ref = C.edge(name).reference()
+        lo = 3
+        hi = lo + len(C.EDGES[name][1])
+        rec = {f: int(ref["out_sessions"][f][1]) for f in R.FIELDS}
+        return (ref["verdicts"][lo:hi] & 0x0F).tolist(), ref["verdicts"][lo:hi].tolist(), ref["pkt_ids"][lo:hi].tolist(), rec, \
+            ref["counts"][1].tolist()
+    v, _, _, rec, cnt = box("free_window_0")
+    assert R.W_SEND not in v and cnt == [0, 5, 10, 0] and rec["inflight"] == 32
+    assert box("exactly_enough_slots")[4] == [10, 3, 0, 0] and box("exactly_enough_slots")[3]["inflight"] == 32
+    assert box("one_slot_too_few")[4] == [9, 3, 1, 0]
+    assert box("inflight_over_max")[4] == [0, 2, 6, 0] and box("inflight_over_max")[3]["inflight"] == 40
+    assert box("inflight_max_0")[4] == [50, 9, 0, 0]
+    ids = [i for i in box("next_pkt_id_65535")[2] if i]
+    assert ids == [65535, 1, 2] and box("next_pkt_id_65535")[3]["next_pkt_id"] == 3
+    ids = [i for i in box("next_pkt_id_65530_10_sends")[2] if i]
+    assert ids == [65530, 65531, 65532, 65533, 65534, 65535, 1, 2, 3, 4]
+    assert box("mq_max_0")[3]["mq_len"] == 37 and box("mq_len_over_max")[3]["mq_len"] == 19
+    _, raw, _, rec, cnt = box("e_is_M-L")
+    assert not any(x & R.W_EVICTS for x in raw) and rec["mq_len"] == 12 and rec["dropped"] == 0 and cnt == [0, 0, 9, 0]
+    _, raw, _, rec, cnt = box("e_is_M-L+1")
+    assert sum(1 for x in raw if x & R.W_EVICTS) == 1 and rec["dropped"] == 1 << 32 and cnt == [0, 0, 10, 1]
+    v, _, _, rec, cnt = box("e_over_M")
+    assert v.count(R.W_QUEUED_DROPPED) == 22 and cnt == [0, 0, 8, 5] and rec["dropped"] == 27 and rec["mq_len"] == 8
+    assert box("disconnected_store_qos0")[4] == [0, 0, 15, 2] and R.W_DROP_QOS0 not in box("disconnected_store_qos0")[0]
+    assert box("disconnected_no_store")[0].count(R.W_DROP_QOS0) == 10
+    assert set(box("not_present")[0]) == {R.W_NO_SESSION, R.W_SKIP_NO_LOCAL, R.W_BAD_MESSAGE}
+    assert set(box("pass")[0]) == {R.W_PASS, R.W_SKIP_NO_LOCAL, R.W_BAD_MESSAGE}
+    for name in ("sub_at_sub_limit", "sub_above_sub_limit"):
+        case = C.edge(name)
+        assert case.reference()["summary"][0] == R.F_BAD_SUB and R.W_NO_SESSION in box(name)[0]
+    assert int(C.edge("sub_at_sub_limit").subs[1]) == C.edge("sub_at_sub_limit").sub_limit
+
+
+def test_edges_across_tile_borders(W):
+    case = C.edges_across_borders()
+    starts = case.offsets[:-1][[i for i, s in enumerate(case.subs) if i % 3 == 2]]
+    ends = case.offsets[1:][[i for i, s in enumerate(case.subs) if i % 3 == 2]]
+    assert len(starts) == len(C.EDGES) and all(int(a) // C.T < (int(b) - 1) // C.T for a, b in zip(starts, ends))
+    got, _ = run(W, case)
+    C.check(case.reference(), got)
+
+
+def test_more_than_65535_sends(W):
+    case = C.more_than_65535_sends()
+    ref = case.reference()
+    assert ref["summary"][7] == 1 and ref["counts"][1][0] == 70_000
+    got, _ = run(W, case)
+    C.check(ref, got)
+
+
+def test_fuzz(W):
+    case = C.fuzz()
+    ref = case.reference()
+    assert ref["summary"][0] == R.F_BAD_SUB and case.m > 200 and set(range(1, 10)) <= set((ref["verdicts"] & 0x0F).tolist())
+    got, _ = run(W, case)
+    C.check(ref, got)
+
+
+def test_update_table_chains_two_batches(W):
+    a, b = C.chained()
+    table = a.table.copy()
+    recs = C.records_of(table)
+    ra = R.run(a.subs, a.offsets, a.opts, recs, update_table=True)
+    mid = C.table_of(recs)
+    assert mid.tobytes() != table.tobytes()
+    got_a, t1 = run(W, a, update_table=True)
+    C.check(a.reference(), got_a)
+    assert [got_a.summary[k] for k in W.SUMMARY] == ra["summary"] and t1.tobytes() == mid.tobytes()
+    h = host(W)
+    from emqx_amd import _lib
+    try:
+        got_b = h.run_host(b.subs, b.offsets, b.opts, t1, update_table=True)
+    except _lib.EngineError as e:
+        got_b = e.partial
+    C.check(b.reference(table=mid), got_b)
+    R.run(b.subs, b.offsets, b.opts, recs, update_table=True)
+    assert t1.tobytes() == C.table_of(recs).tobytes()
+
+
+# ---- refusals and argument errors ---------------------------------------------------------------
+
+def _args(W, case, **over):
+    from emqx_amd import _lib
+    keep = {"subs": case.subs.copy(), "off": case.offsets.copy(), "opts": case.opts.copy(), "table": case.table.copy(),
+            "ver": np.zeros(case.total + 1, dtype=np.uint8), "ids": np.zeros(case.total + 1, dtype=np.uint16),
+            "recs": np.zeros(case.m + 1, dtype=W.SESSION), "cnt": np.zeros((case.m + 1, 4), dtype=np.uint32)}
+    p = lambda a: a.ctypes.data  # noqa: E731
+    kw = dict(inbox_subs=p(keep["subs"]), inbox_offsets=p(keep["off"]), box_opts=p(keep["opts"]), n_boxes=None, m=case.m,
+              cap_in=case.total, cap_boxes=case.m, sessions=p(keep["table"]), sub_limit=case.sub_limit, update_table=0,
+              verdicts=p(keep["ver"]), pkt_ids=p(keep["ids"]), out_sessions=p(keep["recs"]), out_counts=p(keep["cnt"]))
+    kw.update(over)
+    return _lib.WindowBatch(**kw), keep
+
+
+@pytest.mark.parametrize("what", ["no_box_opts", "no_offsets", "no_verdicts", "no_pkt_ids", "no_inbox_subs", "no_out_sessions",
+                                  "no_out_counts", "no_sessions", "m_over_cap_boxes", "cap_in_over", "sub_limit_over"])
+def test_argument_errors(W, what):
+    from emqx_amd import _lib
+    case = C.edge("exactly_enough_slots")
+    over = {"no_box_opts": dict(box_opts=None), "no_offsets": dict(inbox_offsets=None), "no_verdicts": dict(verdicts=None),
+            "no_pkt_ids": dict(pkt_ids=None), "no_inbox_subs": dict(inbox_subs=None), "no_out_sessions": dict(out_sessions=None),
+            "no_out_counts": dict(out_counts=None), "no_sessions": dict(sessions=None), "m_over_cap_boxes": dict(cap_boxes=case.m - 1),
+            "cap_in_over": dict(cap_in=1 << 32), "sub_limit_over": dict(sub_limit=(1 << 32) + 1)}[what]
+    b, keep = _args(W, case, **over)
+    summary = np.full(8, 77, dtype=np.uint64)
+    assert _lib.lib().emqx_window_run_host(host(W)._h, ctypes.byref(b), summary.ctypes.data) == EINVAL
+    assert not keep["ver"].any() and not keep["cnt"].any() and (summary == 77).all()
+    assert _lib.lib().emqx_window_run_host(None, ctypes.byref(b), None) == EINVAL
+
+
+def test_refused_input_writes_only_the_summary(W):
+    from emqx_amd import _lib
+    case = C.edge("e_over_M")
+    for over, words in ((dict(cap_in=case.total - 1), [R.F_INPUT_REFUSED, case.total, case.m, 0, 0, 0, 0, 0]),):
+        b, keep = _args(W, case, **over)
+        summary = np.zeros(8, dtype=np.uint64)
+        assert _lib.lib().emqx_window_run_host(host(W)._h, ctypes.byref(b), summary.ctypes.data) == EINVAL
+        assert summary.tolist() == words == R.run(case.subs, case.offsets, case.opts, [], cap_in=case.total - 1)["summary"]
+        assert not keep["ver"].any() and not keep["ids"].any() and not keep["cnt"].any()
+    # the count read through n_boxes: above cap_boxes it refuses the input
+    count = np.array([case.m + 1], dtype=np.uint64)
+    b, keep = _args(W, case, n_boxes=count.ctypes.data, m=0)
+    summary = np.zeros(8, dtype=np.uint64)
+    assert _lib.lib().emqx_window_run_host(host(W)._h, ctypes.byref(b), summary.ctypes.data) == EINVAL
+    assert summary.tolist() == [R.F_INPUT_REFUSED, 0, case.m + 1, 0, 0, 0, 0, 0] and not keep["ver"].any()
+    count[0] = case.m
+    assert _lib.lib().emqx_window_run_host(host(W)._h, ctypes.byref(b), summary.ctypes.data) == 0
+    assert keep["ver"][:case.total].tobytes() == case.reference()["verdicts"].tobytes() and keep["ver"][case.total] == 0
+
+
+def test_bad_offsets(W):
+    from emqx_amd import _lib
+    h = host(W)
+    t = W.pack_sessions(4)
+    for off in ([0, 2, 1, 3], [1, 2, 3, 3]):
+        with pytest.raises(_lib.EngineError) as e:
+            h.run_host([0, 1, 2], off, [1, 1, 1], t)
+        assert e.value.code == EINVAL
+
+
+def test_tuning_keys(W):
+    from emqx_amd import _lib
+    h = host(W)
+    with pytest.raises(_lib.EngineError) as e:
+        h.set_tuning("no_such_key", 1)
+    assert e.value.code == ENOTFOUND
+    for v in (-1, 2):
+        with pytest.raises(_lib.EngineError) as e:
+            h.set_tuning("path", v)
+        assert e.value.code == EINVAL
+    h.set_tuning("path", 1)
+    assert h.stats()["path"] == 1
+
+
+def test_stats_struct_is_versioned_by_size(W):
+    from emqx_amd import _lib
+    h = host(W)
+    h.run_host([0], [0, 1], [1], W.pack_sessions(1))
+    s = _lib.WindowStats()
+    s.size = 16
+    s.cap_boxes = 12345
+    assert _lib.lib().emqx_window_stats_get(h._h, ctypes.byref(s)) == 0
+    assert s.size == 16 and s.cap_in == 0 and s.cap_boxes == 12345  # nothing beyond 16 bytes written
+    assert h.stats()["calls"] == 1
+    s.size = 4
+    assert _lib.lib().emqx_window_stats_get(h._h, ctypes.byref(s)) == EINVAL

@@ -1,0 +1,218 @@
+"""Cases of the window stage shared by the CPU and the GPU tests: inbox layouts around the tile
+(emqx_amd/csrc/window.h: WN_TILE), the session edges of include/emqx_window.h each in an inbox of
+its own and again in one that crosses a tile border, and a randomised batch.  A case computes its
+reference (tests/window_ref.py) once."""
+
+import numpy as np
+
+from emqx_amd import window as W
+from tests import window_ref as R
+
+T = W.TILE
+NL, BAD = R.DROP_NO_LOCAL, R.BAD_MESSAGE
+P, C, S0, PASS = R.PRESENT, R.CONNECTED, R.STORE_QOS0, R.PASS
+
+
+def session(**kw):
+    rec = dict(inflight=0, inflight_max=32, mq_len=0, mq_max=1000, next_pkt_id=1, flags=P | C, dropped=0)
+    rec.update(kw)
+    return rec
+
+
+def table_of(recs):
+    t = np.zeros(len(recs), dtype=W.SESSION)
+    for i, r in enumerate(recs):
+        for f in R.FIELDS:
+            t[f][i] = r[f]
+    return t
+
+
+def records_of(table):
+    return [{f: int(table[f][i]) for f in R.FIELDS} for i in range(table.size)]
+
+
+def mix(n_pos, n_zero=0, n_skip=0, n_bad=0, seed=1):
+    """Options bytes: n_pos with QoS 1 or 2, n_zero with QoS 0, n_skip dropped by No Local, n_bad
+    bad messages, shuffled."""
+    rng = np.random.default_rng(seed)
+    o = np.concatenate([rng.integers(1, 3, n_pos), np.zeros(n_zero, dtype=np.int64), NL | rng.integers(0, 3, n_skip),
+                        np.full(n_bad, BAD)]).astype(np.uint8)
+    o |= (rng.integers(0, 2, o.size) * 4).astype(np.uint8) * (o != BAD)  # the retain bit rides along
+    rng.shuffle(o)
+    return o
+
+
+class Case:
+    """Inboxes given as (record or None, opts): None is a subscriber id at or above sub_limit."""
+
+    def __init__(self, boxes, spare=3):
+        self.opts = np.concatenate([np.asarray(o, dtype=np.uint8) for _, o in boxes] + [np.zeros(0, dtype=np.uint8)])
+        lens = [len(o) for _, o in boxes]
+        self.offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        recs, subs, bad = [], [], 0
+        for rec, _ in boxes:
+            if rec is None:
+                subs.append(None)
+                continue
+            recs.extend(session(flags=0, mq_len=9) for _ in range(len(recs) % spare))  # ids no inbox names
+            subs.append(len(recs))
+            recs.append(rec)
+        recs.append(session(inflight=5))
+        for k, s in enumerate(subs):
+            if s is None:
+                subs[k] = len(recs) + 5 * bad  # the first of them is sub_limit itself
+                bad += 1
+        self.subs = np.asarray(subs, dtype=np.uint32)
+        self.table = table_of(recs)
+        self.m, self.total, self.sub_limit = len(boxes), int(self.offsets[-1]), len(recs)
+        self._ref = {}
+
+    def reference(self, table=None, update_table=False):
+        """The restatement's answer as arrays; ``table``: another table than the case's own."""
+        key = (None if table is None else table.tobytes(), update_table)
+        if key not in self._ref:
+            recs = records_of(self.table if table is None else table)
+            r = R.run(self.subs, self.offsets, self.opts, recs, update_table=update_table)
+            self._ref[key] = {
+                "verdicts": np.asarray(r["verdicts"], dtype=np.uint8), "pkt_ids": np.asarray(r["pkt_ids"], dtype=np.uint16),
+                "out_sessions": table_of(r["out_sessions"]),
+                "counts": np.asarray(r["counts"], dtype=np.uint32).reshape(-1, 4), "summary": r["summary"],
+                "table": table_of(recs)}
+        return self._ref[key]
+
+
+def check(ref, got):
+    """``got``: an emqx_amd.window.Admitted."""
+    assert [got.summary[k] for k in W.SUMMARY] == ref["summary"], (got.summary, ref["summary"])
+    bad = np.flatnonzero(got.verdicts != ref["verdicts"])
+    assert bad.size == 0, ("verdicts", bad[:8], got.verdicts[bad[:8]], ref["verdicts"][bad[:8]])
+    bad = np.flatnonzero(got.pkt_ids != ref["pkt_ids"])
+    assert bad.size == 0, ("pkt_ids", bad[:8], got.pkt_ids[bad[:8]], ref["pkt_ids"][bad[:8]])
+    assert got.verdicts.dtype == np.uint8 and got.pkt_ids.dtype == np.uint16
+    assert got.out_sessions.tobytes() == ref["out_sessions"].tobytes(), (got.out_sessions, ref["out_sessions"])
+    assert got.counts.tobytes() == ref["counts"].tobytes(), (got.counts, ref["counts"])
+
+
+def same(x, y):
+    assert x.summary == y.summary
+    for a, b in zip(x[:-1], y[:-1]):
+        assert a.tobytes() == b.tobytes()
+
+
+# ---- layouts -----------------------------------------------------------------------------------
+
+def filler(n, seed):
+    return (session(inflight=seed % 30, next_pkt_id=1 + 977 * seed % 65535), mix(n - n // 3, n // 3, seed=seed))
+
+
+def layout(lens, seed=0):
+    """Inboxes of the given lengths over sessions that send, queue and drop."""
+    kinds = [dict(), dict(inflight_max=4, mq_max=3, mq_len=1), dict(flags=P | S0, mq_max=6), dict(flags=P, mq_max=5, mq_len=5),
+             dict(inflight_max=0, next_pkt_id=65533)]
+    return Case([(session(**kinds[(k + seed) % len(kinds)]), mix(n - n // 4, n // 4, seed=seed + k)) for k, n in enumerate(lens)])
+
+
+def split(total, seed):
+    """Inbox lengths that add up to ``total``: mostly short, a few long."""
+    rng = np.random.default_rng(seed)
+    lens = []
+    while sum(lens) < total:
+        lens.append(int(rng.integers(1, 12)) if rng.random() < 0.9 else int(rng.integers(50, 400)))
+    lens[-1] -= sum(lens) - total
+    return [n for n in lens if n > 0]
+
+
+LAYOUTS = {
+    "empty": lambda: Case([]),
+    "inboxes_without_deliveries": lambda: Case([(session(), []), (session(flags=P), [])]),
+    "one_delivery": lambda: layout([1]),
+    "one_inbox_holds_everything": lambda: layout([3 * T + 5], seed=4),
+    "every_inbox_of_length_1": lambda: layout([1] * (T + 9)),
+    "total_T-1": lambda: layout(split(T - 1, 1)),
+    "total_T": lambda: layout(split(T, 2)),
+    "total_T+1": lambda: layout(split(T + 1, 3)),
+    "total_3T+5": lambda: layout(split(3 * T + 5, 4)),
+    "head_and_end_at_a_tile_border": lambda: layout([100, T - 100, 50, T - 50, T, 7], seed=1),
+    "one_inbox_over_3_tiles_between_short_ones": lambda: layout([3, 5, 3 * T + 100, 2, 7], seed=2),
+    "long_inbox_ends_the_batch_at_a_border": lambda: layout([5, 2 * T - 5], seed=3),
+}
+
+# ---- session edges -----------------------------------------------------------------------------
+
+EDGES = {
+    "free_window_0": (session(inflight=32), mix(10, 5)),
+    "exactly_enough_slots": (session(inflight=22), mix(10, 3)),
+    "one_slot_too_few": (session(inflight=23), mix(10, 3)),
+    "inflight_over_max": (session(inflight=40), mix(6, 2)),
+    "inflight_max_0": (session(inflight=7, inflight_max=0), mix(50, 9)),
+    "next_pkt_id_65535": (session(next_pkt_id=65535), mix(3)),
+    "next_pkt_id_65530_10_sends": (session(next_pkt_id=65530, inflight_max=0), mix(10, 2)),
+    "mq_max_0": (session(flags=P | S0, mq_max=0, mq_len=7), mix(20, 10)),
+    "mq_len_over_max": (session(flags=P, mq_max=4, mq_len=10), mix(9, 2)),
+    "e_is_M-L": (session(flags=P, mq_max=12, mq_len=3), mix(9, 4)),
+    "e_is_M-L+1": (session(flags=P, mq_max=12, mq_len=3, dropped=(1 << 32) - 1), mix(10, 4)),
+    "e_over_M": (session(flags=P, mq_max=8, mq_len=5), mix(30, 3)),
+    "disconnected_store_qos0": (session(flags=P | S0, mq_max=15, mq_len=2), mix(10, 10)),
+    "disconnected_no_store": (session(flags=P), mix(10, 10)),
+    "not_present": (session(flags=C | S0), mix(5, 5, 2, 1)),
+    "pass": (session(flags=P | C | PASS), mix(5, 5, 2, 1)),
+    "sub_at_sub_limit": (None, mix(4, 3, 1, 1)),
+    "sub_above_sub_limit": (None, mix(2, 2)),
+    "no_local_and_bad_bytes": (session(inflight_max=4, mq_max=3), mix(8, 4, 5, 4)),
+    "connected_full_then_evicting": (session(inflight_max=2, mq_max=3, mq_len=2), mix(10, 3)),
+    "all_bytes_skipped": (session(), mix(0, 0, 6, 3)),
+}
+
+
+def edge(name):
+    """The edge in an inbox of its own between two short ones."""
+    return Case([filler(3, 1), EDGES[name], filler(2, 2)])
+
+
+def edges_across_borders():
+    """Every edge again, each in an inbox that crosses a tile border: edge i lies around i * T."""
+    boxes, at = [], 0
+    for i, name in enumerate(EDGES):
+        rec, o = EDGES[name]
+        start = (i + 1) * T - len(o) // 2
+        gap = start - at
+        boxes += [filler(gap - 7, 10 + i), filler(7, 40 + i), (rec, o)]
+        at = start + len(o)
+    boxes.append(filler(5, 99))
+    return Case(boxes)
+
+
+def more_than_65535_sends():
+    """70 000 sends from one inbox: the ids wrap past their own start."""
+    return Case([filler(5, 1), (session(inflight_max=0, next_pkt_id=60000), mix(70_000, 11, seed=5)), filler(3, 2)])
+
+
+def fuzz(seed=7, total=6000):
+    """A few thousand deliveries: skewed inbox lengths, random records, every opts byte."""
+    rng = np.random.default_rng(seed)
+    boxes, left = [], total
+    while left > 0:
+        n = min(left, min(int(rng.zipf(1.8)), 300) if rng.random() < 0.995 else int(rng.integers(500, 2500)))
+        rec = session(inflight=int(rng.integers(0, 40)), inflight_max=int(rng.choice([0, 1, 8, 32, 100000])),
+                      mq_len=int(rng.integers(0, 12)), mq_max=int(rng.choice([0, 1, 5, 10, 1000])),
+                      next_pkt_id=int(rng.integers(1, 65536)), flags=int(rng.choice([P | C, P | C, P, P | S0, 0, P | C | PASS])),
+                      dropped=int(rng.integers(0, 1 << 40)))
+        o = rng.integers(0, 256, n).astype(np.uint8)
+        o[rng.random(n) < 0.8] &= 0x0F  # most are plain
+        boxes.append((rec if rng.random() < 0.97 else None, o))
+        left -= n
+    return Case(boxes)
+
+
+def chained(seed=11):
+    """Two batches over one table: the second's inboxes name subscribers of the first's table, most
+    of them ones the first batch changed."""
+    a, b = fuzz(seed, 5000), fuzz(seed + 2, 3000)
+    rng = np.random.default_rng(seed + 1)
+    named = rng.permutation(np.unique(a.subs[a.subs < a.sub_limit]))
+    others = np.setdiff1d(np.arange(a.sub_limit, dtype=np.uint32), named)
+    pool = np.concatenate([named[:int(0.8 * b.m)], rng.permutation(others)])
+    assert pool.size >= b.m
+    b.subs = np.sort(pool[:b.m]).astype(np.uint32)
+    b.table, b.sub_limit = a.table, a.sub_limit
+    return a, b
