@@ -98,6 +98,13 @@ WINDOW_EXPORTS = (
     "emqx_window_run_batch_device", "emqx_window_run_batch_device_async", "emqx_window_run_host",
     "emqx_window_set_tuning", "emqx_window_stats_get",
 )
+# Every symbol include/emqx_route.h declares (dests, aggre/1 and forward lists per node).
+ROUTE_EXPORTS = (
+    "emqx_routetab_create", "emqx_routetab_destroy", "emqx_routetab_add", "emqx_routetab_remove",
+    "emqx_routetab_purge_node", "emqx_routetab_lookup", "emqx_routetab_commit", "emqx_route_batch",
+    "emqx_route_batch_device", "emqx_route_batch_device_async", "emqx_route_host", "emqx_routetab_set_tuning",
+    "emqx_routetab_stats_get",
+)
 
 NO_GROUP = 0xFFFFFFFF
 SHARD_NONE = 0xFFFFFFFF
@@ -297,6 +304,32 @@ class WindowStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
 
 
+class RouteBatch(ctypes.Structure):
+    """struct emqx_route_batch (include/emqx_route.h): the buffers of one route call."""
+    _fields_ = [
+        ("offsets", ctypes.c_void_p), ("filters", ctypes.c_void_p), ("n", ctypes.c_uint64), ("cap_in", ctypes.c_uint64),
+        ("entry_flags", ctypes.c_void_p), ("msg_routes", ctypes.c_void_p), ("node_offsets", ctypes.c_void_p),
+        ("fwd_msgs", ctypes.c_void_p), ("fwd_filters", ctypes.c_void_p), ("cap_fwd", ctypes.c_uint64),
+        ("local_offsets", ctypes.c_void_p), ("local_filters", ctypes.c_void_p),
+    ]
+
+
+class RouteTabStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("n_filters", ctypes.c_uint64), ("n_plain", ctypes.c_uint64), ("n_grouped", ctypes.c_uint64),
+        ("n_nodes", ctypes.c_uint64), ("epoch", ctypes.c_uint64),
+        ("last_build_ms", ctypes.c_double), ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
 class HostBatchStruct(ctypes.Structure):
     """struct emqx_host_batch (include/emqx_match.h): pinned buffers of one host batch."""
     _fields_ = [
@@ -469,6 +502,19 @@ def lib():
         "emqx_window_run_host": (i32, [vp, ctypes.POINTER(WindowBatch), vp]),
         "emqx_window_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_window_stats_get": (i32, [vp, ctypes.POINTER(WindowStats)]),
+        "emqx_routetab_create": (i32, [ctypes.c_int32, u32, ctypes.POINTER(vp)]),
+        "emqx_routetab_destroy": (i32, [vp]),
+        "emqx_routetab_add": (i32, [vp, vp, vp, vp, u64]),
+        "emqx_routetab_remove": (i32, [vp, vp, vp, vp, u64]),
+        "emqx_routetab_purge_node": (i32, [vp, u32, vp, u64, ctypes.POINTER(u64)]),
+        "emqx_routetab_lookup": (i32, [vp, u32, vp, vp, u64, ctypes.POINTER(u64)]),
+        "emqx_routetab_commit": (i32, [vp]),
+        "emqx_route_batch": (i32, [vp, ctypes.POINTER(RouteBatch), ctypes.POINTER(u64), vp]),
+        "emqx_route_batch_device": (i32, [vp, ctypes.POINTER(RouteBatch), ctypes.POINTER(u64), vp, vp]),
+        "emqx_route_batch_device_async": (i32, [vp, ctypes.POINTER(RouteBatch), vp, vp]),
+        "emqx_route_host": (i32, [vp, ctypes.POINTER(RouteBatch), ctypes.POINTER(u64), vp]),
+        "emqx_routetab_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_routetab_stats_get": (i32, [vp, vp]),
         "emqx_commit_stats": (i32, [vp, vp, u32]),
         "emqx_shard_owner": (i32, [vp, vp, u64, u32, u32, i32, vp]),
         "emqx_shard_owner_device": (i32, [vp, vp, u64, u32, u32, vp, vp]),
