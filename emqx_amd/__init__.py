@@ -14,6 +14,8 @@ Modules mirror the reference's Erlang modules on the hot path:
                           batch's deliveries grouped by subscriber, in batch order)
   :mod:`emqx_amd.window`  emqx_session deliver/2 + enqueue/2, emqx_inflight is_full/1, emqx_mqueue in/2 (inflight and
                           mqueue admission of every inbox: packet ids, what is queued, what is dropped)
+  :mod:`emqx_amd.ack`     emqx_session puback/2 + pubrec/2 + pubcomp/2 + batch_n/1 over emqx_inflight (which packet ids
+                          are inflight per session; a batch of acks against them: reason codes, refs, the freed window)
   :mod:`emqx_amd.route`   emqx_broker aggre/1 + route/2 + do_route/2, emqx_router_helper cleanup_routes/1 (the route
                           bag in device memory: routes per message, forward lists per node, the local CSR)
   :mod:`emqx_amd.dist`    multi-GPU: replicated tables + data-parallel topic split,
@@ -27,4 +29,5 @@ from .deliver import SubOpts  # noqa: F401,E402  (delivery options behind the fa
 from .select import HookIndex, OwnerTable  # noqa: F401,E402  (hook consumers selected per publish)
 from .inbox import Inbox  # noqa: F401,E402  (a batch's deliveries grouped by subscriber)
 from .window import Window  # noqa: F401,E402  (inflight and mqueue admission per inbox)
+from .ack import Ack  # noqa: F401,E402  (inflight slots and PUBACK / PUBREC / PUBCOMP per session)
 from .route import ClusterRouter, RouteTable  # noqa: F401,E402  (dests, aggre/1 and forward lists per node)

@@ -98,6 +98,12 @@ WINDOW_EXPORTS = (
     "emqx_window_run_batch_device", "emqx_window_run_batch_device_async", "emqx_window_run_host",
     "emqx_window_set_tuning", "emqx_window_stats_get",
 )
+# Every symbol include/emqx_ack.h declares (inflight slots and PUBACK / PUBREC / PUBCOMP per session).
+ACK_EXPORTS = (
+    "emqx_ack_create", "emqx_ack_destroy", "emqx_ack_reserve", "emqx_ack_record_batch", "emqx_ack_record_batch_device",
+    "emqx_ack_record_batch_device_async", "emqx_ack_record_host", "emqx_ack_run_batch", "emqx_ack_run_batch_device",
+    "emqx_ack_run_batch_device_async", "emqx_ack_run_host", "emqx_ack_set_tuning", "emqx_ack_stats_get",
+)
 # Every symbol include/emqx_route.h declares (dests, aggre/1 and forward lists per node).
 ROUTE_EXPORTS = (
     "emqx_routetab_create", "emqx_routetab_destroy", "emqx_routetab_add", "emqx_routetab_remove",
@@ -294,6 +300,46 @@ class WindowStats(ctypes.Structure):
         ("size", ctypes.c_uint64),
         ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64),
         ("path", ctypes.c_uint64), ("calls", ctypes.c_uint64), ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
+class AckRecordArgs(ctypes.Structure):
+    """struct emqx_ack_record_args (include/emqx_ack.h): the buffers of one record call."""
+    _fields_ = [
+        ("inbox_subs", ctypes.c_void_p), ("inbox_offsets", ctypes.c_void_p), ("box_opts", ctypes.c_void_p),
+        ("n_boxes", ctypes.c_void_p),
+        ("m", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("verdicts", ctypes.c_void_p), ("pkt_ids", ctypes.c_void_p), ("refs", ctypes.c_void_p),
+        ("slots", ctypes.c_void_p), ("w", ctypes.c_uint64), ("sub_limit", ctypes.c_uint64),
+        ("out_unrecorded", ctypes.c_void_p),
+    ]
+
+
+class AckRunArgs(ctypes.Structure):
+    """struct emqx_ack_run_args (include/emqx_ack.h): the buffers of one run call."""
+    _fields_ = [
+        ("ack_subs", ctypes.c_void_p), ("ack_offsets", ctypes.c_void_p), ("acks", ctypes.c_void_p),
+        ("n_boxes", ctypes.c_void_p),
+        ("m", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("update_table", ctypes.c_uint64),
+        ("slots", ctypes.c_void_p), ("w", ctypes.c_uint64),
+        ("verdicts", ctypes.c_void_p), ("out_refs", ctypes.c_void_p), ("out_counts", ctypes.c_void_p),
+    ]
+
+
+class AckStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64), ("w", ctypes.c_uint64),
+        ("scratch_bytes", ctypes.c_uint64), ("rematch", ctypes.c_uint64), ("calls", ctypes.c_uint64),
+        ("last_call_ms", ctypes.c_double),
     ]
 
     def __init__(self, *a, **kw):
@@ -502,6 +548,19 @@ def lib():
         "emqx_window_run_host": (i32, [vp, ctypes.POINTER(WindowBatch), vp]),
         "emqx_window_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_window_stats_get": (i32, [vp, ctypes.POINTER(WindowStats)]),
+        "emqx_ack_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_ack_destroy": (i32, [vp]),
+        "emqx_ack_reserve": (i32, [vp, u64, u64, u64]),
+        "emqx_ack_record_batch": (i32, [vp, ctypes.POINTER(AckRecordArgs), vp]),
+        "emqx_ack_record_batch_device": (i32, [vp, ctypes.POINTER(AckRecordArgs), vp, vp]),
+        "emqx_ack_record_batch_device_async": (i32, [vp, ctypes.POINTER(AckRecordArgs), vp, vp]),
+        "emqx_ack_record_host": (i32, [vp, ctypes.POINTER(AckRecordArgs), vp]),
+        "emqx_ack_run_batch": (i32, [vp, ctypes.POINTER(AckRunArgs), vp]),
+        "emqx_ack_run_batch_device": (i32, [vp, ctypes.POINTER(AckRunArgs), vp, vp]),
+        "emqx_ack_run_batch_device_async": (i32, [vp, ctypes.POINTER(AckRunArgs), vp, vp]),
+        "emqx_ack_run_host": (i32, [vp, ctypes.POINTER(AckRunArgs), vp]),
+        "emqx_ack_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_ack_stats_get": (i32, [vp, ctypes.POINTER(AckStats)]),
         "emqx_routetab_create": (i32, [ctypes.c_int32, u32, ctypes.POINTER(vp)]),
         "emqx_routetab_destroy": (i32, [vp]),
         "emqx_routetab_add": (i32, [vp, vp, vp, vp, u64]),

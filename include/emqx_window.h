@@ -71,7 +71,8 @@
  * Out of scope, kept by the caller: priority tables (p_table; mark such sessions PASS), the
  * shared-subscription ack and nack path (maybe_ack / maybe_nack, off by default), message expiry,
  * active_n slicing of an inbox, the ack-driven dequeue/1 and retry, which ids are still inflight
- * (only the count is modelled), the id-to-pid lookup and the send.
+ * (only the count is modelled; emqx_ack.h keeps the ids and takes the acks), the id-to-pid lookup
+ * and the send.
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_inbox.h: the
  * calls on one handle share its device scratch and are ordered by the handle.
