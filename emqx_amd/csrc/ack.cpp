@@ -49,6 +49,7 @@ struct emqx_ack {
   int device = EMQX_ACK_HOST_ONLY;
   std::mutex mu;  // the calls of a handle, its scratch and its stats
   int64_t rematch = 0;
+  int64_t max_blocks = AK_MAX_BLOCKS, scan_chunk = AK_SCAN_BLOCK;
   uint64_t calls = 0;
   double last_call_ms = 0;
   uint64_t cap_in = 0, cap_boxes = 0, w = 0, scratch_bytes = 0;  // what the scratch takes
@@ -439,7 +440,8 @@ int launch(emqx_ack* h, const emqx_ack_record_args* b, uint8_t* p, const Layout&
   a.masks = reinterpret_cast<uint64_t*>(p + l.tiles + l.heads);
   a.ctr = reinterpret_cast<unsigned long long*>(p + l.bytes - l.ctr);
   a.summary = summary;
-  (void)h;
+  a.max_blocks = static_cast<uint32_t>(h->max_blocks);
+  a.scan_chunk = static_cast<uint32_t>(h->scan_chunk);
   return ak_launch_record(a, s);
 }
 
@@ -465,6 +467,7 @@ int launch(emqx_ack* h, const emqx_ack_run_args* b, uint8_t* p, const Layout& l,
   a.comp = reinterpret_cast<uint32_t*>(p + l.tiles + l.heads + l.masks + l.mins);
   a.ctr = reinterpret_cast<unsigned long long*>(p + l.bytes - l.ctr);
   a.summary = summary;
+  a.max_blocks = static_cast<uint32_t>(h->max_blocks);
   return ak_launch_run(a, s);
 }
 
@@ -731,10 +734,24 @@ int run_batch(emqx_ack* h, const emqx_ack_run_args* b, uint64_t* summary_out) {
 
 int ack_set_tuning(emqx_ack* h, const char* key, int64_t value) {
   if (!h || !key) return EMQX_EINVAL;
-  if (std::strcmp(key, "rematch") != 0) return EMQX_ENOTFOUND;
-  if (value < 0 || value > 1) return EMQX_EINVAL;
+  int64_t* field;
+  int64_t lo = 1, hi;
+  if (std::strcmp(key, "rematch") == 0) {
+    field = &h->rematch;
+    lo = 0;
+    hi = 1;
+  } else if (std::strcmp(key, "max_blocks") == 0) {  // read at enqueue; a host-only handle has no grid
+    field = &h->max_blocks;
+    hi = AK_MAX_BLOCKS;
+  } else if (std::strcmp(key, "scan_chunk") == 0) {
+    field = &h->scan_chunk;
+    hi = AK_SCAN_BLOCK;
+  } else {
+    return EMQX_ENOTFOUND;
+  }
+  if (value < lo || value > hi) return EMQX_EINVAL;
   std::lock_guard<std::mutex> g(h->mu);
-  h->rematch = value;
+  *field = value;
   return EMQX_OK;
 }
 

@@ -33,6 +33,10 @@ constexpr uint32_t AK_ROWS = 4;                       // consecutive acks or del
 constexpr uint32_t AK_TILE = AK_BLOCK * AK_ROWS;      // per tile (1024)
 constexpr uint64_t AK_MAX_TOTAL = (1ull << 32) - 1;   // positions and inbox indices are 32-bit
 constexpr uint64_t AK_MAX_ACKS = (1ull << 31) - 1;    // a rank and one bit share 32 bits
+// Tuning (emqx_ack_set_tuning): the largest grid of the by-tile and by-row passes, beyond which
+// the blocks stride, and the tile totals record's one-block scan takes per carry step.
+constexpr uint32_t AK_MAX_BLOCKS = 4096;
+constexpr uint32_t AK_SCAN_BLOCK = 1024;
 constexpr uint32_t AK_NONE = 0xFFFFFFFFu;
 
 // phase of a slot (EMQX_ACK_*), kind of an ack, the verdict byte (EMQX_A_*)
@@ -152,6 +156,8 @@ struct AkRecArgs {
   uint64_t* masks;          // [cap_boxes] the EMPTY slots of the inbox's row at entry
   unsigned long long* ctr;  // [AK_S_WORDS] counters, zeroed by the scan kernel
   uint64_t* summary;        // device or host-pinned, written last with plain stores
+  uint32_t max_blocks;      // grid cap of every pass whose blocks stride
+  uint32_t scan_chunk;      // tile totals per carry step of the scan, 1..AK_SCAN_BLOCK
 };
 // Of a run call.
 struct AkRunArgs {
@@ -174,6 +180,7 @@ struct AkRunArgs {
   uint32_t* comp;           // [cap_boxes * w]
   unsigned long long* ctr;  // [AK_S_WORDS] counters, zeroed by the init kernel
   uint64_t* summary;
+  uint32_t max_blocks;  // grid cap of every pass whose blocks stride
 };
 int ak_launch_record(const AkRecArgs& a, void* stream);
 int ak_launch_run(const AkRunArgs& a, void* stream);

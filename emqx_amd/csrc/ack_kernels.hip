@@ -41,8 +41,6 @@ namespace emqx {
 namespace {
 
 constexpr uint32_t AK_WAVES = AK_BLOCK / 64;
-constexpr uint32_t AK_MAX_BLOCKS = 4096;  // the blocks stride over the tiles or rows beyond this
-constexpr uint32_t AK_SCAN_BLOCK = 1024;
 constexpr uint8_t AK_NO_SLOT = 0xFF;
 
 // m and offsets[m] when this call may use them; false: the call is refused.
@@ -189,7 +187,8 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_rec_heads_kernel(AkRecArgs a) {
   }
 }
 
-// One block: tile_tot becomes its exclusive scan.
+// One block: tile_tot becomes its exclusive scan, scan_chunk tiles a carry step: a thread at or
+// beyond the chunk adds 0 and stores nothing.
 __global__ __launch_bounds__(AK_SCAN_BLOCK) void ack_rec_scan_kernel(AkRecArgs a) {
   __shared__ uint32_t wsum[AK_SCAN_BLOCK / 64];
   if (threadIdx.x < AK_S_WORDS) a.ctr[threadIdx.x] = 0;
@@ -197,10 +196,12 @@ __global__ __launch_bounds__(AK_SCAN_BLOCK) void ack_rec_scan_kernel(AkRecArgs a
   if (!ak_rec_counts(a, &m, &total)) return;
   const uint64_t tiles = ak_tiles_eff(total);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t chunk = a.scan_chunk && a.scan_chunk < AK_SCAN_BLOCK ? a.scan_chunk : AK_SCAN_BLOCK;
   uint32_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += AK_SCAN_BLOCK) {
+  for (uint64_t base = 0; base < tiles; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint32_t x = t < tiles ? a.tile_tot[t] : 0u;
+    const bool mine = threadIdx.x < chunk && t < tiles;
+    const uint32_t x = mine ? a.tile_tot[t] : 0u;
     uint32_t incl = x;
     for (uint32_t d = 1; d < 64; d <<= 1) {
       const uint32_t y = __shfl_up(incl, d, 64);
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(AK_SCAN_BLOCK) void ack_rec_scan_kernel(AkRecArgs a
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < tiles) a.tile_tot[t] = carry + before + incl - x;
+    if (mine) a.tile_tot[t] = carry + before + incl - x;
     carry += all;
     __syncthreads();
   }
@@ -573,9 +574,11 @@ __global__ void ack_run_finish_kernel(AkRunArgs a) {
   for (uint32_t k = 0; k < AK_S_WORDS; ++k) a.summary[k] = s[k];
 }
 
-uint32_t ak_grid(uint64_t units) {
+// The grid over `units` tiles or groups of rows; the blocks stride beyond the cap.
+uint32_t ak_grid(uint64_t units, uint32_t max_blocks) {
+  const uint32_t cap = max_blocks && max_blocks < AK_MAX_BLOCKS ? max_blocks : AK_MAX_BLOCKS;
   if (units == 0) units = 1;
-  return static_cast<uint32_t>(units < AK_MAX_BLOCKS ? units : AK_MAX_BLOCKS);
+  return static_cast<uint32_t>(units < cap ? units : cap);
 }
 
 }  // namespace
@@ -583,8 +586,8 @@ uint32_t ak_grid(uint64_t units) {
 // Enqueues the passes of one record call.
 int ak_launch_record(const AkRecArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const uint32_t tiles = ak_grid(ak_tiles(a.cap_in));
-  const uint32_t rows = ak_grid((a.cap_boxes + AK_BLOCK / (a.w / 2) - 1) / (AK_BLOCK / (a.w / 2)));
+  const uint32_t tiles = ak_grid(ak_tiles(a.cap_in), a.max_blocks);
+  const uint32_t rows = ak_grid((a.cap_boxes + AK_BLOCK / (a.w / 2) - 1) / (AK_BLOCK / (a.w / 2)), a.max_blocks);
   ack_rec_heads_kernel<<<dim3(tiles), dim3(AK_BLOCK), 0, s>>>(a);
   ack_rec_scan_kernel<<<dim3(1), dim3(AK_SCAN_BLOCK), 0, s>>>(a);
   ack_rec_rows_kernel<<<dim3(rows), dim3(AK_BLOCK), 0, s>>>(a);
@@ -596,9 +599,9 @@ int ak_launch_record(const AkRecArgs& a, void* stream) {
 // Enqueues the passes of one run call.
 int ak_launch_run(const AkRunArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const uint32_t tiles = ak_grid(ak_tiles(a.cap_in));
-  const uint32_t rows = ak_grid((a.cap_boxes + AK_BLOCK / (a.w / 2) - 1) / (AK_BLOCK / (a.w / 2)));
-  ack_run_init_kernel<<<dim3(ak_grid((a.cap_boxes * a.w / 4 + AK_BLOCK - 1) / AK_BLOCK)), dim3(AK_BLOCK), 0, s>>>(a);
+  const uint32_t tiles = ak_grid(ak_tiles(a.cap_in), a.max_blocks);
+  const uint32_t rows = ak_grid((a.cap_boxes + AK_BLOCK / (a.w / 2) - 1) / (AK_BLOCK / (a.w / 2)), a.max_blocks);
+  ack_run_init_kernel<<<dim3(ak_grid((a.cap_boxes * a.w / 4 + AK_BLOCK - 1) / AK_BLOCK, a.max_blocks)), dim3(AK_BLOCK), 0, s>>>(a);
   ack_run_first_kernel<<<dim3(tiles), dim3(AK_BLOCK), 0, s>>>(a);
   ack_run_comp_kernel<<<dim3(tiles), dim3(AK_BLOCK), 0, s>>>(a);
   ack_run_verdict_kernel<<<dim3(tiles), dim3(AK_BLOCK), 0, s>>>(a);

@@ -114,6 +114,8 @@ struct emqx_subopts {
   uint64_t epoch = 0;
   double last_build_ms = 0, last_call_ms = 0;
   std::atomic<int64_t> max_load_pct{50};
+  std::atomic<int64_t> max_blocks{DV_MAX_BLOCKS};
+  std::atomic<int64_t> scan_chunk{DV_SCAN_BLOCK};
 #ifndef EMQX_DELIVER_NO_DEVICE
   std::mutex pmu;  // work pool
   std::vector<std::unique_ptr<Work>> pool;
@@ -367,7 +369,7 @@ void release(emqx_subopts* h, Work* w) {
 
 // Zeroes the counters on the stream and enqueues the passes.  The scratch of a call that has
 // drained is free to grow: nothing on the device still reads it.
-int enqueue(const Snapshot& sn, Work* w, const emqx_deliver_batch* b, uint64_t* summary, hipStream_t s) {
+int enqueue(emqx_subopts* h, const Snapshot& sn, Work* w, const emqx_deliver_batch* b, uint64_t* summary, hipStream_t s) {
   const uint64_t tiles = (b->cap_in + DV_TILE - 1) / DV_TILE;
   if (b->kept_offsets && w->tiles_cap < tiles) {
     if (w->d_tile_kept) (void)hipFree(w->d_tile_kept);
@@ -403,6 +405,8 @@ int enqueue(const Snapshot& sn, Work* w, const emqx_deliver_batch* b, uint64_t* 
   a.tile_kept = w->d_tile_kept;
   a.tile_base = w->d_tile_base;
   a.summary = summary;
+  a.max_blocks = static_cast<uint32_t>(h->max_blocks.load(std::memory_order_relaxed));
+  a.scan_chunk = static_cast<uint32_t>(h->scan_chunk.load(std::memory_order_relaxed));
   DV_TRY(hipMemsetAsync(w->d_ctr, 0, DV_S_WORDS * sizeof(unsigned long long), s));
   return dv_launch(a, s) == 0 ? EMQX_OK : EMQX_EDEVICE;
 }
@@ -418,7 +422,7 @@ int enrich_batch_device_async(emqx_subopts* h, const emqx_deliver_batch* b, uint
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : w->stream;
   int rc = EMQX_OK;
   if (!stream && after_null_stream(s) != hipSuccess) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = enqueue(*sn, w, b, summary, s);
+  if (rc == EMQX_OK) rc = enqueue(h, *sn, w, b, summary, s);
   if (hipEventRecord(w->done, s) != hipSuccess) {
     (void)hipStreamSynchronize(s);
     rc = EMQX_EDEVICE;
@@ -452,7 +456,7 @@ int enrich_batch_device(emqx_subopts* h, const emqx_deliver_batch* b, uint64_t* 
   uint64_t sum[DV_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   int rc = EMQX_OK;
   if (!stream && after_null_stream(s) != hipSuccess) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = enqueue(*sn, w, b, d_sum, s);
+  if (rc == EMQX_OK) rc = enqueue(h, *sn, w, b, d_sum, s);
   if (rc == EMQX_OK && hipMemcpyAsync(sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s) != hipSuccess) rc = EMQX_EDEVICE;
   if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;
   release(h, w);
@@ -525,7 +529,7 @@ int enrich_batch(emqx_subopts* h, const emqx_deliver_batch* b, uint64_t* n_kept,
     bool ok = up(o_off, b->offsets, (n + 1) * 8) && up(o_subs, b->subs, total * 4) && up(o_fil, b->filters, total * 4) &&
               up(o_qos, b->msg_qos, n) && up(o_flags, b->msg_flags, n) && up(o_from, b->msg_from, b->msg_from ? n * 4 : 0);
     if (!ok) rc = EMQX_EDEVICE;
-    if (rc == EMQX_OK) rc = enqueue(*sn, w, &d, d_sum, s);
+    if (rc == EMQX_OK) rc = enqueue(h, *sn, w, &d, d_sum, s);
     if (rc == EMQX_OK) {
       ok = down(b->out_opts, o_out, total) && down(b->out_subids, o_osid, b->out_subids ? total * 4 : 0) &&
            down(b->kept_offsets, o_koff, compact ? (n + 1) * 8 : 0) &&
@@ -555,10 +559,22 @@ int enrich_batch(emqx_subopts* h, const emqx_deliver_batch* b, uint64_t* n_kept,
 
 int sub_set_tuning(emqx_subopts* h, const char* key, int64_t value) {
   if (!h || !key) return EMQX_EINVAL;
-  if (std::strcmp(key, "max_load_pct") != 0) return EMQX_ENOTFOUND;
-  if (value < 10 || value > 95) return EMQX_EINVAL;
-  h->max_load_pct.store(value, std::memory_order_relaxed);
-  return EMQX_OK;
+  if (std::strcmp(key, "max_load_pct") == 0) {
+    if (value < 10 || value > 95) return EMQX_EINVAL;
+    h->max_load_pct.store(value, std::memory_order_relaxed);
+    return EMQX_OK;
+  }
+  if (std::strcmp(key, "max_blocks") == 0) {  // read at enqueue; a host-only handle has no grid
+    if (value < 1 || value > DV_MAX_BLOCKS) return EMQX_EINVAL;
+    h->max_blocks.store(value, std::memory_order_relaxed);
+    return EMQX_OK;
+  }
+  if (std::strcmp(key, "scan_chunk") == 0) {
+    if (value < 1 || value > DV_SCAN_BLOCK) return EMQX_EINVAL;
+    h->scan_chunk.store(value, std::memory_order_relaxed);
+    return EMQX_OK;
+  }
+  return EMQX_ENOTFOUND;
 }
 
 int sub_stats_get(emqx_subopts* h, emqx_subopts_stats* out) {

@@ -21,6 +21,10 @@ constexpr uint32_t DV_SUB_QOS = 0x03u, DV_SUB_NL = 0x04u, DV_SUB_RAP = 0x08u, DV
 constexpr uint32_t DV_MSG_RETAIN = 0x01u, DV_MSG_RETAINED = 0x02u;
 constexpr uint32_t DV_OUT_RETAIN = 0x04u, DV_OUT_NL = 0x08u, DV_OUT_DROP = 0x10u, DV_OUT_NO_SUBOPTS = 0x20u, DV_OUT_BAD = 0x40u;
 constexpr uint32_t DV_F_KEPT_OVERFLOW = 1u, DV_F_INPUT_REFUSED = 2u;
+// Tuning (emqx_subopts_set_tuning): the largest grid of the by-tile passes, beyond which the
+// blocks stride over the tiles, and the tile totals the one-block scan takes per carry step.
+constexpr uint32_t DV_MAX_BLOCKS = 16384;
+constexpr uint32_t DV_SCAN_BLOCK = 1024;
 // words of the device counters / the summary
 enum { DV_S_FLAGS = 0, DV_S_TOTAL = 1, DV_S_KEPT = 2, DV_S_DROPPED = 3, DV_S_NO_SUBOPTS = 4, DV_S_QOS0 = 5, DV_S_WORDS = 8 };
 
@@ -137,6 +141,8 @@ struct DvArgs {
   uint32_t* tile_kept;      // [ceil(cap_in / DV_TILE)] kept deliveries per tile
   uint64_t* tile_base;      // [same] exclusive scan of tile_kept
   uint64_t* summary;        // device or host-pinned, written last with plain stores
+  uint32_t max_blocks;      // grid cap of the by-tile passes
+  uint32_t scan_chunk;      // tile totals per carry step of the scan, 1..DV_SCAN_BLOCK
 };
 constexpr uint32_t DV_TILE = 256;  // deliveries per tile = threads per block
 int dv_launch(const DvArgs& a, void* stream);

@@ -31,7 +31,6 @@ namespace emqx {
 namespace {
 
 constexpr uint32_t DV_WAVES = DV_TILE / 64;
-constexpr uint32_t DV_MAX_BLOCKS = 16384;  // the blocks stride over the tiles beyond this
 
 // offsets[n] when it is a delivery count this call may use, else ~0 (the call is refused).
 __device__ inline uint64_t dv_total(const DvArgs& a) {
@@ -82,18 +81,20 @@ __global__ __launch_bounds__(DV_TILE) void deliver_eval_kernel(DvArgs a) {
   if (threadIdx.x < 6 && acc) atomicAdd(a.ctr + DV_S_KEPT + threadIdx.x, static_cast<unsigned long long>(acc));
 }
 
-// One block: tile_base = exclusive scan of tile_kept over the tiles of this call.
-constexpr uint32_t DV_SCAN_BLOCK = 1024;
+// One block: tile_base = exclusive scan of tile_kept over the tiles of this call, scan_chunk
+// tiles a carry step: a thread at or beyond the chunk adds 0 and stores nothing.
 __global__ __launch_bounds__(DV_SCAN_BLOCK) void deliver_scan_kernel(DvArgs a) {
   __shared__ uint64_t wsum[DV_SCAN_BLOCK / 64];
   const uint64_t total = dv_total(a);
   if (total == ~0ull) return;
   const uint64_t n_tiles = (total + DV_TILE - 1) / DV_TILE;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t chunk = a.scan_chunk && a.scan_chunk < DV_SCAN_BLOCK ? a.scan_chunk : DV_SCAN_BLOCK;
   uint64_t carry = 0;
-  for (uint64_t base = 0; base < n_tiles; base += DV_SCAN_BLOCK) {
+  for (uint64_t base = 0; base < n_tiles; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint64_t x = t < n_tiles ? a.tile_kept[t] : 0;
+    const bool mine = threadIdx.x < chunk && t < n_tiles;
+    const uint64_t x = mine ? a.tile_kept[t] : 0;
     uint64_t incl = x;
     for (uint32_t d = 1; d < 64; d <<= 1) {
       const uint64_t y = __shfl_up(incl, d);
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(DV_SCAN_BLOCK) void deliver_scan_kernel(DvArgs a) {
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < n_tiles) a.tile_base[t] = carry + before + incl - x;
+    if (mine) a.tile_base[t] = carry + before + incl - x;
     carry += all;
     __syncthreads();
   }
@@ -183,7 +184,8 @@ __global__ __launch_bounds__(DV_TILE) void deliver_finish_kernel(DvArgs a) {
 int dv_launch(const DvArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint64_t tiles = (a.cap_in + DV_TILE - 1) / DV_TILE;
-  const uint32_t blocks = static_cast<uint32_t>(tiles < DV_MAX_BLOCKS ? tiles : DV_MAX_BLOCKS);
+  const uint32_t cap = a.max_blocks && a.max_blocks < DV_MAX_BLOCKS ? a.max_blocks : DV_MAX_BLOCKS;
+  const uint32_t blocks = static_cast<uint32_t>(tiles < cap ? tiles : cap);
   if (a.n && blocks) {
     deliver_eval_kernel<<<dim3(blocks), dim3(DV_TILE), 0, s>>>(a);
     if (a.kept_offsets) {

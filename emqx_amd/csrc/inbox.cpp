@@ -33,6 +33,7 @@ struct emqx_inbox {
   int device = EMQX_INBOX_HOST_ONLY;
   std::mutex mu;  // the calls of a handle, its scratch and its stats
   int64_t path = 0;
+  int64_t max_blocks = IB_MAX_BLOCKS, scan_chunk = IB_SCAN_BLOCK;
   uint64_t calls = 0, last_passes = 0;
   double last_call_ms = 0;
   uint64_t cap_in = 0, sub_limit = 0, scratch_bytes = 0;  // what the scratch takes
@@ -339,6 +340,8 @@ int enqueue(emqx_inbox* h, const emqx_inbox_batch* b, uint64_t* summary, hipStre
   a.sort_temp = take(l.temp);
   a.sort_temp_bytes = h->temp_bytes;
   a.summary = summary ? summary : d_sum;
+  a.max_blocks = static_cast<uint32_t>(h->max_blocks);
+  a.scan_chunk = static_cast<uint32_t>(h->scan_chunk);
   if (d_sum_out) *d_sum_out = d_sum;
   if (h->inflight) IB_TRY(hipStreamWaitEvent(s, h->done, 0));
   IB_TRY(hipMemsetAsync(zero, 0, ZERO_BYTES, s));
@@ -481,10 +484,24 @@ int group_batch(emqx_inbox* h, const emqx_inbox_batch* b, uint64_t* n_boxes, uin
 
 int inbox_set_tuning(emqx_inbox* h, const char* key, int64_t value) {
   if (!h || !key) return EMQX_EINVAL;
-  if (std::strcmp(key, "path") != 0) return EMQX_ENOTFOUND;
-  if (value < 0 || value > 1) return EMQX_EINVAL;
+  int64_t* field;
+  int64_t lo = 1, hi;
+  if (std::strcmp(key, "path") == 0) {
+    field = &h->path;
+    lo = 0;
+    hi = 1;
+  } else if (std::strcmp(key, "max_blocks") == 0) {  // read at enqueue; a host-only handle has no grid
+    field = &h->max_blocks;
+    hi = IB_MAX_BLOCKS;
+  } else if (std::strcmp(key, "scan_chunk") == 0) {
+    field = &h->scan_chunk;
+    hi = IB_SCAN_BLOCK;
+  } else {
+    return EMQX_ENOTFOUND;
+  }
+  if (value < lo || value > hi) return EMQX_EINVAL;
   std::lock_guard<std::mutex> g(h->mu);
-  h->path = value;
+  *field = value;
   return EMQX_OK;
 }
 

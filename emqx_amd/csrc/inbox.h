@@ -26,6 +26,11 @@ constexpr uint32_t IB_ROWS = 8;                          // rows per tile
 constexpr uint32_t IB_TILE = IB_BLOCK * IB_ROWS;         // deliveries per tile of every pass (2048)
 constexpr uint64_t IB_MAX_TOTAL = (1ull << 32) - 1;      // positions and message indices are 32-bit
 constexpr uint64_t IB_MAX_SUB_LIMIT = 1ull << 32;
+// Tuning (emqx_inbox_set_tuning): the largest grid of the by-tile and by-row passes, beyond which
+// the blocks stride, and the tile totals a one-block scan takes per carry step.
+constexpr uint32_t IB_MAX_BLOCKS = 16384;
+constexpr uint32_t IB_LONGEST_BLOCKS = 1024;             // the longest pass never takes more
+constexpr uint32_t IB_SCAN_BLOCK = 1024;
 
 // Key bits that can differ below sub_limit (1..2^32): ceil(log2(sub_limit)).
 IB_HD inline uint32_t ib_key_bits(uint64_t sub_limit) {
@@ -86,6 +91,8 @@ struct IbArgs {
   void* sort_temp;       // path 1: the library sort's temporary storage
   uint64_t sort_temp_bytes;
   uint64_t* summary;     // device or host-pinned, written last with plain stores
+  uint32_t max_blocks;   // grid cap of every pass whose blocks stride
+  uint32_t scan_chunk;   // tile totals per carry step of the scans, 1..IB_SCAN_BLOCK
 };
 int ib_launch(const IbArgs& a, int path, void* stream);
 // Temporary storage of path 1's sort over cap_in pairs on the key bits of sub_limit.

@@ -42,8 +42,6 @@ namespace emqx {
 namespace {
 
 constexpr uint32_t IB_WAVES = IB_BLOCK / 64;
-constexpr uint32_t IB_MAX_BLOCKS = 16384;  // the blocks stride over the tiles beyond this
-constexpr uint32_t IB_SCAN_BLOCK = 1024;
 static_assert(IB_RADIX == IB_BLOCK, "thread t owns digit t");
 
 // offsets[n] when it is a delivery count this call may use, else ~0 (the call is refused).
@@ -130,6 +128,12 @@ __global__ __launch_bounds__(IB_BLOCK) void inbox_hist_kernel(IbArgs a, uint32_t
   if (FIRST) ib_first_report(a, msgs, bad);
 }
 
+// Tile totals a one-block scan takes per carry step: a thread at or beyond it adds 0 and stores
+// nothing, but takes part in the shuffles and barriers.
+__device__ inline uint32_t ib_chunk(const IbArgs& a) {
+  return a.scan_chunk && a.scan_chunk < IB_SCAN_BLOCK ? a.scan_chunk : IB_SCAN_BLOCK;
+}
+
 // Block `digit`: tile_hist[digit][*] becomes the position of the digit's first delivery of each
 // tile: the deliveries of the lower digits, then the digit's deliveries of the earlier tiles.
 __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_scan_kernel(IbArgs a, uint32_t pass) {
@@ -146,9 +150,11 @@ __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_scan_kernel(IbArgs a, uin
   for (uint32_t w = 0; w < IB_SCAN_BLOCK / 64; ++w) carry += wsum[w];
   __syncthreads();
   uint32_t* hist = a.tile_hist + static_cast<uint64_t>(digit) * tiles;
-  for (uint64_t base = 0; base < tiles; base += IB_SCAN_BLOCK) {
+  const uint32_t chunk = ib_chunk(a);
+  for (uint64_t base = 0; base < tiles; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint32_t x = t < tiles ? hist[t] : 0u;
+    const bool mine = threadIdx.x < chunk && t < tiles;
+    const uint32_t x = mine ? hist[t] : 0u;
     uint32_t incl = x;
     for (uint32_t d = 1; d < 64; d <<= 1) {
       const uint32_t y = __shfl_up(incl, d, 64);
@@ -161,7 +167,7 @@ __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_scan_kernel(IbArgs a, uin
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < tiles) hist[t] = carry + before + incl - x;
+    if (mine) hist[t] = carry + before + incl - x;
     carry += all;
     __syncthreads();
   }
@@ -327,10 +333,12 @@ __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_hscan_kernel(IbArgs a) {
   if (total == ~0ull) return;
   const uint64_t tiles = ib_tiles(total);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t chunk = ib_chunk(a);
   uint32_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += IB_SCAN_BLOCK) {
+  for (uint64_t base = 0; base < tiles; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint32_t x = t < tiles ? a.tile_heads[t] : 0u;
+    const bool mine = threadIdx.x < chunk && t < tiles;
+    const uint32_t x = mine ? a.tile_heads[t] : 0u;
     uint32_t incl = x;
     for (uint32_t d = 1; d < 64; d <<= 1) {
       const uint32_t y = __shfl_up(incl, d, 64);
@@ -343,7 +351,7 @@ __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_hscan_kernel(IbArgs a) {
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < tiles) a.tile_hbase[t] = carry + before + incl - x;
+    if (mine) a.tile_hbase[t] = carry + before + incl - x;
     carry += all;
     __syncthreads();
   }
@@ -451,7 +459,8 @@ uint64_t ib_sort_temp_bytes(uint64_t cap_in, uint64_t sub_limit) {
 int ib_launch(const IbArgs& a, int path, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint64_t tiles = ib_tiles(a.cap_in);
-  const uint32_t blocks = static_cast<uint32_t>(tiles < IB_MAX_BLOCKS ? tiles : IB_MAX_BLOCKS);
+  const uint32_t cap = a.max_blocks && a.max_blocks < IB_MAX_BLOCKS ? a.max_blocks : IB_MAX_BLOCKS;
+  const uint32_t blocks = static_cast<uint32_t>(tiles < cap ? tiles : cap);
   if (a.n && blocks) {
     const uint32_t passes = ib_passes(a.sub_limit);
     const uint32_t* sorted;
@@ -463,7 +472,7 @@ int ib_launch(const IbArgs& a, int path, void* stream) {
       starts = a.idx[(passes - 1) & 1];  // the last pass reads the other one and writes neither
     } else {
       const uint64_t rows = (a.cap_in + IB_BLOCK - 1) / IB_BLOCK;
-      const uint32_t flat = static_cast<uint32_t>(rows < IB_MAX_BLOCKS ? rows : IB_MAX_BLOCKS);
+      const uint32_t flat = static_cast<uint32_t>(rows < cap ? rows : cap);
       inbox_prep_kernel<<<dim3(flat), dim3(IB_BLOCK), 0, s>>>(a);
       size_t tb = a.sort_temp_bytes;
       const hipError_t e = rocprim::radix_sort_pairs(a.sort_temp, tb, a.key[0], a.key[1], a.idx[0], a.idx[1],
@@ -477,7 +486,8 @@ int ib_launch(const IbArgs& a, int path, void* stream) {
     inbox_hscan_kernel<<<dim3(1), dim3(IB_SCAN_BLOCK), 0, s>>>(a);
     inbox_starts_kernel<<<dim3(blocks), dim3(IB_BLOCK), 0, s>>>(a, sorted, starts);
     const uint64_t rows = (a.cap_in + IB_BLOCK - 1) / IB_BLOCK;
-    inbox_longest_kernel<<<dim3(static_cast<uint32_t>(rows < 1024 ? rows : 1024)), dim3(IB_BLOCK), 0, s>>>(a, starts);
+    const uint32_t lcap = cap < IB_LONGEST_BLOCKS ? cap : IB_LONGEST_BLOCKS;
+    inbox_longest_kernel<<<dim3(static_cast<uint32_t>(rows < lcap ? rows : lcap)), dim3(IB_BLOCK), 0, s>>>(a, starts);
   }
   inbox_finish_kernel<<<dim3(1), dim3(64), 0, s>>>(a);
   return static_cast<int>(hipGetLastError());

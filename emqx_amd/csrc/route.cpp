@@ -107,6 +107,7 @@ struct emqx_routetab {
   uint64_t epoch = 0;
   double last_build_ms = 0, last_call_ms = 0;
   std::atomic<int64_t> max_blocks{16384};
+  std::atomic<int64_t> scan_chunk{RT_SCAN_BLOCK};
   std::atomic<int64_t> path{0};
   std::atomic<int64_t> stored_mask{1};  // measured: level with the re-gather at 1 M slots, 8 % ahead at 10 M
 #ifndef EMQX_ROUTE_NO_DEVICE
@@ -482,6 +483,7 @@ int enqueue(emqx_routetab* h, const Snapshot& sn, Work* w, const RouteBatch* b, 
   a.sort_temp_bytes = temp_bytes;
   a.summary = summary;
   a.max_blocks = static_cast<uint32_t>(h->max_blocks.load(std::memory_order_relaxed));
+  a.scan_chunk = static_cast<uint32_t>(h->scan_chunk.load(std::memory_order_relaxed));
   RT_TRY(hipMemsetAsync(w->d_ctr, 0, RT_C_WORDS * sizeof(unsigned long long), s));
   return rt_launch(a, path, s) == 0 ? EMQX_OK : EMQX_EDEVICE;
 }
@@ -629,6 +631,11 @@ int tab_set_tuning(emqx_routetab* h, const char* key, int64_t value) {
   if (std::strcmp(key, "max_blocks") == 0) {
     if (value < 1 || value > 16384) return EMQX_EINVAL;
     h->max_blocks.store(value, std::memory_order_relaxed);
+    return EMQX_OK;
+  }
+  if (std::strcmp(key, "scan_chunk") == 0) {
+    if (value < 1 || value > RT_SCAN_BLOCK) return EMQX_EINVAL;
+    h->scan_chunk.store(value, std::memory_order_relaxed);
     return EMQX_OK;
   }
   if (std::strcmp(key, "stored_mask") == 0) {

@@ -66,6 +66,9 @@ RT_HD inline uint64_t rt_find_msg(const uint64_t* offsets, uint64_t n, uint64_t 
   return lo;
 }
 
+// Tuning key "scan_chunk": the elements the one-block scans take per carry step, at most this.
+constexpr uint32_t RT_SCAN_BLOCK = 1024;
+
 #if defined(__HIPCC__)
 constexpr uint32_t RT_BLOCK = 256, RT_ROWS = 8, RT_TILE = RT_BLOCK * RT_ROWS;  // 2 048 entries a tile
 constexpr uint32_t RT_PAD_KEY = RT_NODES;  // path 1: sorts behind every node under 7 key bits
@@ -105,6 +108,7 @@ struct RtArgs {
   uint64_t sort_temp_bytes;
   uint64_t* summary;    // device or host-pinned, written last with plain stores
   uint32_t max_blocks;  // grid cap of the by-tile passes
+  uint32_t scan_chunk;  // elements per carry step of the scans, 1..RT_SCAN_BLOCK
 };
 uint64_t rt_sort_temp_bytes(uint64_t cap_fwd);
 int rt_launch(const RtArgs& a, int path, void* stream);

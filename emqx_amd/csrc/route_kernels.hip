@@ -49,7 +49,6 @@ namespace {
 
 constexpr uint32_t RT_WAVES = RT_BLOCK / 64;
 constexpr uint32_t RT_CHUNKS = RT_ROWS * RT_WAVES;
-constexpr uint32_t RT_SCAN_BLOCK = 1024;
 constexpr uint32_t RT_FLAT_BLOCKS = 1024;  // grid cap of the by-message and by-forward passes
 static_assert(RT_CHUNKS <= 64 && RT_NODES == 64, "one lane a chunk, one lane a node");
 
@@ -241,13 +240,15 @@ __global__ __launch_bounds__(RT_BLOCK) void route_count_kernel(RtArgs a) {
   if (lane == 0 && unknown) atomicAdd(a.ctr + RT_S_UNKNOWN, static_cast<unsigned long long>(unknown));
 }
 
-// One block: x[0, m) becomes its exclusive scan; returns the sum in every thread.
-__device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum) {
+// One block: x[0, m) becomes its exclusive scan, `chunk` elements a carry step (a thread at or
+// beyond the chunk adds 0 and stores nothing); returns the sum in every thread.
+__device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum, uint32_t chunk) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint64_t carry = 0;
-  for (uint64_t base = 0; base < m; base += RT_SCAN_BLOCK) {
+  for (uint64_t base = 0; base < m; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint64_t v = t < m ? x[t] : 0;
+    const bool mine = threadIdx.x < chunk && t < m;
+    const uint64_t v = mine ? x[t] : 0;
     const uint64_t incl = wave_incl_scan(v);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
@@ -256,7 +257,7 @@ __device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < m) x[t] = carry + before + incl - v;
+    if (mine) x[t] = carry + before + incl - v;
     carry += all;
     __syncthreads();
   }
@@ -268,11 +269,12 @@ __global__ __launch_bounds__(RT_SCAN_BLOCK) void route_scan_kernel(RtArgs a) {
   const uint64_t total = rt_total(a);
   if (total == ~0ull) return;
   const uint64_t tiles = rt_tiles(total);
-  const uint64_t fwd = scan_in_place(a.tile_hist, RT_NODES * tiles, wsum);
-  (void)scan_in_place(a.tile_routes, tiles, wsum);
-  const uint64_t kept = scan_in_place(a.tile_kept, tiles, wsum);
-  (void)scan_in_place(a.tile_hasfwd, tiles, wsum);
-  (void)scan_in_place(a.tile_fwd, tiles, wsum);
+  const uint32_t chunk = a.scan_chunk && a.scan_chunk < RT_SCAN_BLOCK ? a.scan_chunk : RT_SCAN_BLOCK;
+  const uint64_t fwd = scan_in_place(a.tile_hist, RT_NODES * tiles, wsum, chunk);
+  (void)scan_in_place(a.tile_routes, tiles, wsum, chunk);
+  const uint64_t kept = scan_in_place(a.tile_kept, tiles, wsum, chunk);
+  (void)scan_in_place(a.tile_hasfwd, tiles, wsum, chunk);
+  (void)scan_in_place(a.tile_fwd, tiles, wsum, chunk);
   if (threadIdx.x < RT_NODES) a.node_offsets[threadIdx.x] = a.tile_hist[static_cast<uint64_t>(threadIdx.x) * tiles];
   if (threadIdx.x == 0) {
     a.node_offsets[RT_NODES] = fwd;

@@ -106,6 +106,7 @@ struct emqx_owntab {
   uint64_t epoch = 0;
   double last_build_ms = 0, last_call_ms = 0;
   std::atomic<int64_t> max_blocks{16384};
+  std::atomic<int64_t> scan_chunk{SL_SCAN_BLOCK};
 #ifndef EMQX_SELECT_NO_DEVICE
   std::mutex pmu;  // work pool
   std::vector<std::unique_ptr<Work>> pool;
@@ -436,6 +437,7 @@ int enqueue(emqx_owntab* h, const Snapshot& sn, Work* w, const SelBatch* b, uint
   a.ma_before = reinterpret_cast<uint64_t*>(w->d_scratch + o_before);
   a.summary = summary;
   a.max_blocks = static_cast<uint32_t>(h->max_blocks.load(std::memory_order_relaxed));
+  a.scan_chunk = static_cast<uint32_t>(h->scan_chunk.load(std::memory_order_relaxed));
   SL_TRY(hipMemsetAsync(w->d_ctr, 0, SL_C_WORDS * sizeof(unsigned long long), s));
   return sl_launch(a, s) == 0 ? EMQX_OK : EMQX_EDEVICE;
 }
@@ -568,10 +570,17 @@ int select_batch(emqx_owntab* h, const SelBatch* b, uint64_t* n_out, uint64_t* s
 
 int own_set_tuning(emqx_owntab* h, const char* key, int64_t value) {
   if (!h || !key) return EMQX_EINVAL;
-  if (std::strcmp(key, "max_blocks") != 0) return EMQX_ENOTFOUND;
-  if (value < 1 || value > 16384) return EMQX_EINVAL;
-  h->max_blocks.store(value, std::memory_order_relaxed);
-  return EMQX_OK;
+  if (std::strcmp(key, "max_blocks") == 0) {
+    if (value < 1 || value > 16384) return EMQX_EINVAL;
+    h->max_blocks.store(value, std::memory_order_relaxed);
+    return EMQX_OK;
+  }
+  if (std::strcmp(key, "scan_chunk") == 0) {
+    if (value < 1 || value > SL_SCAN_BLOCK) return EMQX_EINVAL;
+    h->scan_chunk.store(value, std::memory_order_relaxed);
+    return EMQX_OK;
+  }
+  return EMQX_ENOTFOUND;
 }
 
 int own_stats_get(emqx_owntab* h, emqx_owntab_stats* out) {

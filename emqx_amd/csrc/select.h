@@ -143,6 +143,9 @@ SL_HD inline uint64_t sl_find_msg(const uint64_t* offsets, uint64_t n, uint64_t 
   return lo;
 }
 
+// Tuning key "scan_chunk": the elements the one-block scans take per carry step, at most this.
+constexpr uint32_t SL_SCAN_BLOCK = 1024;
+
 #if defined(__HIPCC__)
 // Arguments of the device passes (select_kernels.hip); the pointers are emqx_select_batch's.
 struct SlArgs {
@@ -161,6 +164,7 @@ struct SlArgs {
   uint64_t* ma_before;      // [n] match-all owners of the earlier messages of the same tile
   uint64_t* summary;        // device or host-pinned, written last with plain stores
   uint32_t max_blocks;      // grid cap of the by-entry passes
+  uint32_t scan_chunk;      // elements per carry step of the scans, 1..SL_SCAN_BLOCK
 };
 constexpr uint32_t SL_TILE = 256;  // entries (messages) per tile = threads per block
 int sl_launch(const SlArgs& a, void* stream);

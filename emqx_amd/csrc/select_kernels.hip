@@ -40,7 +40,6 @@ namespace emqx {
 namespace {
 
 constexpr uint32_t SL_WAVES = SL_TILE / 64;
-constexpr uint32_t SL_SCAN_BLOCK = 1024;
 constexpr uint32_t SL_MSG_BLOCKS = 16384;  // grid cap of the by-message passes
 
 // offsets[n] when it is an entry count this call may use, else ~0 (the call is refused).
@@ -126,13 +125,15 @@ __global__ __launch_bounds__(SL_TILE) void select_macount_kernel(SlArgs a) {
   }
 }
 
-// One block: x[0, m) becomes its exclusive scan; returns the sum in every thread.
-__device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum) {
+// One block: x[0, m) becomes its exclusive scan, `chunk` elements a carry step (a thread at or
+// beyond the chunk adds 0 and stores nothing); returns the sum in every thread.
+__device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum, uint32_t chunk) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint64_t carry = 0;
-  for (uint64_t base = 0; base < m; base += SL_SCAN_BLOCK) {
+  for (uint64_t base = 0; base < m; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint64_t v = t < m ? x[t] : 0;
+    const bool mine = threadIdx.x < chunk && t < m;
+    const uint64_t v = mine ? x[t] : 0;
     uint64_t incl = v;
     for (uint32_t d = 1; d < 64; d <<= 1) {
       const uint64_t y = __shfl_up(incl, d);
@@ -145,7 +146,7 @@ __device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < m) x[t] = carry + before + incl - v;
+    if (mine) x[t] = carry + before + incl - v;
     carry += all;
     __syncthreads();
   }
@@ -156,8 +157,9 @@ __global__ __launch_bounds__(SL_SCAN_BLOCK) void select_scan_kernel(SlArgs a) {
   __shared__ uint64_t wsum[SL_SCAN_BLOCK / 64];
   const uint64_t total = sl_total(a);
   if (total == ~0ull) return;
-  const uint64_t by_entry = scan_in_place(a.tile_base, (total + SL_TILE - 1) / SL_TILE, wsum);
-  const uint64_t by_all = scan_in_place(a.mtile_base, (a.n + SL_TILE - 1) / SL_TILE, wsum);
+  const uint32_t chunk = a.scan_chunk && a.scan_chunk < SL_SCAN_BLOCK ? a.scan_chunk : SL_SCAN_BLOCK;
+  const uint64_t by_entry = scan_in_place(a.tile_base, (total + SL_TILE - 1) / SL_TILE, wsum, chunk);
+  const uint64_t by_all = scan_in_place(a.mtile_base, (a.n + SL_TILE - 1) / SL_TILE, wsum, chunk);
   if (threadIdx.x == 0) {
     a.ctr[SL_C_ENTRY_TOTAL] = by_entry;
     a.ctr[SL_S_SELECTED] = by_entry + by_all;

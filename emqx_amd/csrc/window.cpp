@@ -42,6 +42,7 @@ struct emqx_window {
   int device = EMQX_WINDOW_HOST_ONLY;
   std::mutex mu;  // the calls of a handle, its scratch and its stats
   int64_t path = 0;
+  int64_t max_blocks = WN_MAX_BLOCKS, scan_chunk = WN_SCAN_BLOCK;
   uint64_t calls = 0;
   double last_call_ms = 0;
   uint64_t cap_in = 0, cap_boxes = 0, scratch_bytes = 0;  // what the scratch takes
@@ -307,6 +308,8 @@ int enqueue(emqx_window* h, const emqx_window_batch* b, uint64_t* summary, hipSt
   a.ctr = reinterpret_cast<unsigned long long*>(p + l.tiles + l.heads);
   uint64_t* d_sum = reinterpret_cast<uint64_t*>(p + l.tiles + l.heads) + WN_S_WORDS;
   a.summary = summary ? summary : d_sum;
+  a.max_blocks = static_cast<uint32_t>(h->max_blocks);
+  a.scan_chunk = static_cast<uint32_t>(h->scan_chunk);
   if (d_sum_out) *d_sum_out = d_sum;
   if (h->inflight) WN_TRY(hipStreamWaitEvent(s, h->done, 0));
   const int rc = wn_launch(a, static_cast<int>(h->path), s) == 0 ? EMQX_OK : EMQX_EDEVICE;
@@ -455,10 +458,24 @@ int run_batch(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out)
 
 int window_set_tuning(emqx_window* h, const char* key, int64_t value) {
   if (!h || !key) return EMQX_EINVAL;
-  if (std::strcmp(key, "path") != 0) return EMQX_ENOTFOUND;
-  if (value < 0 || value > 1) return EMQX_EINVAL;
+  int64_t* field;
+  int64_t lo = 1, hi;
+  if (std::strcmp(key, "path") == 0) {
+    field = &h->path;
+    lo = 0;
+    hi = 1;
+  } else if (std::strcmp(key, "max_blocks") == 0) {  // read at enqueue; a host-only handle has no grid
+    field = &h->max_blocks;
+    hi = WN_MAX_BLOCKS;
+  } else if (std::strcmp(key, "scan_chunk") == 0) {
+    field = &h->scan_chunk;
+    hi = WN_SCAN_BLOCK;
+  } else {
+    return EMQX_ENOTFOUND;
+  }
+  if (value < lo || value > hi) return EMQX_EINVAL;
   std::lock_guard<std::mutex> g(h->mu);
-  h->path = value;
+  *field = value;
   return EMQX_OK;
 }
 

@@ -25,6 +25,11 @@ constexpr uint32_t WN_BLOCK = 256;                   // threads per block
 constexpr uint32_t WN_ROWS = 8;                      // consecutive deliveries per thread
 constexpr uint32_t WN_TILE = WN_BLOCK * WN_ROWS;     // deliveries per tile (2048)
 constexpr uint64_t WN_MAX_TOTAL = (1ull << 32) - 1;  // positions, ranks and inbox indices are 32-bit
+// Tuning (emqx_window_set_tuning): the largest grid of the by-tile and by-row passes, beyond which
+// the blocks stride, and the tile totals the one-block scan takes per carry step.
+constexpr uint32_t WN_MAX_BLOCKS = 2048;
+constexpr uint32_t WN_WAVE_BLOCKS = 16384;  // path 1's wave kernel while max_blocks is at its maximum
+constexpr uint32_t WN_SCAN_BLOCK = 1024;
 
 // the verdict byte (EMQX_W_*)
 constexpr uint8_t WN_SEND_QOS0 = 1, WN_SEND = 2, WN_QUEUED = 3, WN_QUEUED_DROPPED = 4, WN_DROP_QOS0 = 5,
@@ -176,6 +181,8 @@ struct WnArgs {
   uint64_t* head_pre;   // [cap_boxes + 1] live counts between the tile's start and the inbox's head
   unsigned long long* ctr;  // [WN_S_WORDS] counters, zeroed by the scan kernel
   uint64_t* summary;    // device or host-pinned, written last with plain stores
+  uint32_t max_blocks;  // grid cap of every pass whose blocks stride
+  uint32_t scan_chunk;  // tile totals per carry step of the scan, 1..WN_SCAN_BLOCK
 };
 int wn_launch(const WnArgs& a, int path, void* stream);
 #endif

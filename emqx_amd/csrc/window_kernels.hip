@@ -41,8 +41,6 @@ namespace emqx {
 namespace {
 
 constexpr uint32_t WN_WAVES = WN_BLOCK / 64;
-constexpr uint32_t WN_MAX_BLOCKS = 2048;  // the blocks stride over the tiles beyond this
-constexpr uint32_t WN_SCAN_BLOCK = 1024;
 constexpr uint32_t WN_NONE = ~0u;
 
 // m and inbox_offsets[m] when this call may use them; false: the call is refused.
@@ -150,7 +148,8 @@ __global__ __launch_bounds__(WN_BLOCK) void window_heads_kernel(WnArgs a) {
   }
 }
 
-// One block: tile_tot becomes its exclusive scan (neither half reaches 2^32: no carry between them).
+// One block: tile_tot becomes its exclusive scan (neither half reaches 2^32: no carry between them),
+// scan_chunk tiles a carry step: a thread at or beyond the chunk adds 0 and stores nothing.
 __global__ __launch_bounds__(WN_SCAN_BLOCK) void window_scan_kernel(WnArgs a) {
   __shared__ uint64_t wsum[WN_SCAN_BLOCK / 64];
   if (threadIdx.x < WN_S_WORDS) a.ctr[threadIdx.x] = 0;
@@ -158,10 +157,12 @@ __global__ __launch_bounds__(WN_SCAN_BLOCK) void window_scan_kernel(WnArgs a) {
   if (!wn_counts(a, &m, &total)) return;
   const uint64_t tiles = wn_tiles_eff(total);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t chunk = a.scan_chunk && a.scan_chunk < WN_SCAN_BLOCK ? a.scan_chunk : WN_SCAN_BLOCK;
   uint64_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += WN_SCAN_BLOCK) {
+  for (uint64_t base = 0; base < tiles; base += chunk) {
     const uint64_t t = base + threadIdx.x;
-    const uint64_t x = t < tiles ? a.tile_tot[t] : 0ull;
+    const bool mine = threadIdx.x < chunk && t < tiles;
+    const uint64_t x = mine ? a.tile_tot[t] : 0ull;
     uint64_t incl = x;
     for (uint32_t d = 1; d < 64; d <<= 1) {
       const uint64_t y = __shfl_up(incl, d, 64);
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(WN_SCAN_BLOCK) void window_scan_kernel(WnArgs a) {
       if (w < wave) before += wsum[w];
       all += wsum[w];
     }
-    if (t < tiles) a.tile_tot[t] = carry + before + incl - x;
+    if (mine) a.tile_tot[t] = carry + before + incl - x;
     carry += all;
     __syncthreads();
   }
@@ -443,20 +444,23 @@ __global__ void window_finish_kernel(WnArgs a) {
 // Enqueues the passes of one call.
 int wn_launch(const WnArgs& a, int path, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
+  // below its maximum the key caps every grid; at it (the default) the wave kernel keeps its own cap
+  const bool capped = a.max_blocks && a.max_blocks < WN_MAX_BLOCKS;
+  const uint32_t cap = capped ? a.max_blocks : WN_MAX_BLOCKS, wave_cap = capped ? a.max_blocks : WN_WAVE_BLOCKS;
   if (path == 0) {
     const uint64_t tiles = wn_tiles(a.cap_in) ? wn_tiles(a.cap_in) : 1;
-    const uint32_t blocks = static_cast<uint32_t>(tiles < WN_MAX_BLOCKS ? tiles : WN_MAX_BLOCKS);
+    const uint32_t blocks = static_cast<uint32_t>(tiles < cap ? tiles : cap);
     window_heads_kernel<<<dim3(blocks), dim3(WN_BLOCK), 0, s>>>(a);
     window_scan_kernel<<<dim3(1), dim3(WN_SCAN_BLOCK), 0, s>>>(a);
     window_verdict_kernel<<<dim3(blocks), dim3(WN_BLOCK), 0, s>>>(a);
   } else {
     const uint64_t rows = (a.cap_boxes + WN_WAVES - 1) / WN_WAVES;
     window_zero_kernel<<<dim3(1), dim3(64), 0, s>>>(a);
-    if (rows) window_wave_kernel<<<dim3(static_cast<uint32_t>(rows < 16384 ? rows : 16384)), dim3(WN_BLOCK), 0, s>>>(a);
+    if (rows) window_wave_kernel<<<dim3(static_cast<uint32_t>(rows < wave_cap ? rows : wave_cap)), dim3(WN_BLOCK), 0, s>>>(a);
   }
   if (a.update_table && a.cap_boxes) {
     const uint64_t rows = (a.cap_boxes + WN_BLOCK - 1) / WN_BLOCK;
-    window_writeback_kernel<<<dim3(static_cast<uint32_t>(rows < WN_MAX_BLOCKS ? rows : WN_MAX_BLOCKS)), dim3(WN_BLOCK), 0, s>>>(a);
+    window_writeback_kernel<<<dim3(static_cast<uint32_t>(rows < cap ? rows : cap)), dim3(WN_BLOCK), 0, s>>>(a);
   }
   window_finish_kernel<<<dim3(1), dim3(64), 0, s>>>(a);
   return static_cast<int>(hipGetLastError());

@@ -234,9 +234,15 @@ int emqx_ack_run_batch_device(emqx_ack* h, const emqx_ack_run_args* b, uint64_t*
 int emqx_ack_run_batch_device_async(emqx_ack* h, const emqx_ack_run_args* b, uint64_t* summary, void* stream);
 int emqx_ack_run_host(emqx_ack* h, const emqx_ack_run_args* b, uint64_t* summary_out);
 
-/* Key "rematch": 0 (default) the verdict buffer carries an ack's matched slot between the passes
+/* Keys: "rematch": 0 (default) the verdict buffer carries an ack's matched slot between the passes
  * of a run call; 1 every pass matches the ack against its row again (the same bytes, more row
- * reads).  EMQX_ENOTFOUND for unknown keys. */
+ * reads); "max_blocks" (1..4096, default 4096): the grid cap of every pass whose blocks stride
+ * (the tile passes of record and run, run's init pass and both rows kernels), the blocks stride
+ * over the tiles or rows beyond it; "scan_chunk" (1..1024, default 1024): the tile totals record's
+ * one-block scan takes per carry step (tests lower both to make the blocks stride and the scan
+ * carry at small shapes; the same bytes at every value).  Both are read when a call is enqueued;
+ * a host-only handle accepts and ignores them.  EMQX_EINVAL out of range, EMQX_ENOTFOUND for
+ * unknown keys. */
 int emqx_ack_set_tuning(emqx_ack* h, const char* key, int64_t value);
 int emqx_ack_stats_get(emqx_ack* h, emqx_ack_stats* out);
 

@@ -174,8 +174,13 @@ int emqx_deliver_enrich_batch_device_async(emqx_subopts* h, const emqx_deliver_b
  * same predicate code the kernels run: the per-call path and the checker of the batch path. */
 int emqx_deliver_enrich_host(emqx_subopts* h, const emqx_deliver_batch* b, uint64_t* n_kept, uint64_t* summary_out);
 
-/* Key "max_load_pct" (10..95, default 50): the fill of the hash table the next commit builds
- * (tests raise it to lengthen the probe runs).  EMQX_ENOTFOUND for unknown keys. */
+/* Keys: "max_load_pct" (10..95, default 50): the fill of the hash table the next commit builds
+ * (tests raise it to lengthen the probe runs); "max_blocks" (1..16384, default 16384): the grid cap
+ * of the by-tile passes (evaluate and scatter), the blocks stride over the tiles beyond it;
+ * "scan_chunk" (1..1024, default 1024): the tile totals the one-block scan takes per carry step
+ * (tests lower both to make the blocks stride and the scan carry at small shapes; the same bytes
+ * at every value).  Both are read when a call is enqueued; a host-only handle accepts and ignores
+ * them.  EMQX_EINVAL out of range, EMQX_ENOTFOUND for unknown keys. */
 int emqx_subopts_set_tuning(emqx_subopts* h, const char* key, int64_t value);
 int emqx_subopts_stats_get(emqx_subopts* h, emqx_subopts_stats* out);
 

@@ -141,8 +141,15 @@ int emqx_inbox_group_batch_device_async(emqx_inbox* h, const emqx_inbox_batch* b
  * batch path.  Returns as emqx_inbox_group_batch. */
 int emqx_inbox_group_host(emqx_inbox* h, const emqx_inbox_batch* b, uint64_t* n_boxes, uint64_t* summary_out);
 
-/* Key "path": 0 the stage's own radix passes (default), 1 the library radix sort followed by one
- * gather kernel (the yardstick; both produce the same bytes).  EMQX_ENOTFOUND for unknown keys. */
+/* Keys: "path": 0 the stage's own radix passes (default), 1 the library radix sort followed by one
+ * gather kernel (the yardstick; both produce the same bytes); "max_blocks" (1..16384, default
+ * 16384): the grid cap of every pass whose blocks stride (the histogram and scatter of every radix
+ * pass, the heads, the starts, path 1's prep and gather, and the longest pass, which never takes
+ * more than 1024), the blocks stride over the tiles or rows beyond it; "scan_chunk" (1..1024,
+ * default 1024): the tile totals the one-block scans take per carry step (tests lower both to make
+ * the blocks stride and the scans carry at small shapes; the same bytes at every value).  Both are
+ * read when a call is enqueued; a host-only handle accepts and ignores them.  EMQX_EINVAL out of
+ * range, EMQX_ENOTFOUND for unknown keys. */
 int emqx_inbox_set_tuning(emqx_inbox* h, const char* key, int64_t value);
 int emqx_inbox_stats_get(emqx_inbox* h, emqx_inbox_stats* out);
 

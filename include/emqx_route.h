@@ -165,7 +165,9 @@ int emqx_route_batch_device_async(emqx_routetab* h, const struct emqx_route_batc
 int emqx_route_host(emqx_routetab* h, const struct emqx_route_batch* b, uint64_t* n_fwd, uint64_t* summary_out);
 
 /* Keys: "max_blocks" (1..16384, default 16384): the grid cap of the by-tile passes, the blocks
- * stride over the tiles beyond it; "path" (0: ballot ranks, the default; 1: expand, library
+ * stride over the tiles beyond it; "scan_chunk" (1..1024, default 1024): the elements the one-block
+ * scans take per carry step (tests lower both to make the blocks stride and the scans carry at
+ * small shapes; the same bytes at every value); "path" (0: ballot ranks, the default; 1: expand, library
  * radix sort, gather: the yardstick; both write the same bytes); "stored_mask" (1, the default: the
  * second by-tile pass reads a word the first stored per entry, 8 bytes of scratch per entry of
  * cap_in; 0: it gathers the records again; the same bytes either way).  EMQX_ENOTFOUND for unknown keys. */

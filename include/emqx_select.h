@@ -147,9 +147,10 @@ int emqx_select_batch_device_async(emqx_owntab* h, const struct emqx_select_batc
  * predicate code the kernels run: the per-call path and the checker of the batch path. */
 int emqx_select_host(emqx_owntab* h, const struct emqx_select_batch* b, uint64_t* n_out, uint64_t* summary_out);
 
-/* Key "max_blocks" (1..16384, default 16384): the grid cap of the by-entry passes; the blocks
- * stride over the tiles beyond it (tests lower it to make them stride).  EMQX_ENOTFOUND for
- * unknown keys. */
+/* Keys: "max_blocks" (1..16384, default 16384): the grid cap of the by-entry passes; the blocks
+ * stride over the tiles beyond it (tests lower it to make them stride); "scan_chunk" (1..1024,
+ * default 1024): the tile totals the one-block scans take per carry step (tests lower it to make
+ * them carry; the same bytes at every value).  EMQX_ENOTFOUND for unknown keys. */
 int emqx_owntab_set_tuning(emqx_owntab* h, const char* key, int64_t value);
 int emqx_owntab_stats_get(emqx_owntab* h, emqx_owntab_stats* out);
 

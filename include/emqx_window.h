@@ -204,8 +204,14 @@ int emqx_window_run_batch_device_async(emqx_window* h, const emqx_window_batch* 
  * path.  Returns as emqx_window_run_batch. */
 int emqx_window_run_host(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out);
 
-/* Key "path": 0 the tile scan (default), 1 one wave per inbox (the yardstick: its time grows with
- * the longest inbox; both produce the same bytes).  EMQX_ENOTFOUND for unknown keys. */
+/* Keys: "path": 0 the tile scan (default), 1 one wave per inbox (the yardstick: its time grows with
+ * the longest inbox; both produce the same bytes); "max_blocks" (1..2048, default 2048): the grid
+ * cap of every pass whose blocks stride (the heads, the verdicts, the write-back and path 1's wave
+ * kernel), the blocks stride over the tiles or inboxes beyond it; at 2048 the wave kernel keeps its
+ * own cap of 16384; "scan_chunk" (1..1024, default 1024): the tile totals the one-block scan takes
+ * per carry step (tests lower both to make the blocks stride and the scan carry at small shapes;
+ * the same bytes at every value).  Both are read when a call is enqueued; a host-only handle
+ * accepts and ignores them.  EMQX_EINVAL out of range, EMQX_ENOTFOUND for unknown keys. */
 int emqx_window_set_tuning(emqx_window* h, const char* key, int64_t value);
 int emqx_window_stats_get(emqx_window* h, emqx_window_stats* out);
 

@@ -238,6 +238,48 @@ def fuzz(seed=3, n_sessions=2500, w=16):
     return RunCase(sessions, w)
 
 
+def strided_run(w=16):
+    """7 T + 5 acks over more than 100 sessions, for a grid capped below the 8 tiles and the four
+    or more groups of rows: one list over tiles 0, 1 and 2 with the PUBREC and the PUBCOMP of one
+    slot in different tiles (in order twice, the PUBCOMP first once); lists that start exactly at
+    3 T, 5 T and 6 T; empty lists at the 3 T border and behind the last ack; a session that is not
+    present whose list crosses the 4 T border; a subscriber beyond the table."""
+    sessions, at = [], [0]
+
+    def add(session):
+        sessions.append(session)
+        at[0] += len(session[2])
+
+    def fill_to(pos):
+        while at[0] < pos:
+            k = len(sessions)
+            add(mixed_list(min(pos - at[0], 20 + 7 * k % 31), seed=9000 + 100 * w + k, w=w))
+
+    add(filler(1, w))  # two acks: rank i of the next list is position 2 + i
+    pairs = [(ACK, 60000 + i % 5000) for i in range(2 * T + 200)]
+    pairs[10], pairs[T + 10] = (REC, 5), (COMP, 5)          # tiles 0 and 1
+    pairs[T + 20], pairs[2 * T + 20] = (REC, 6), (COMP, 6)  # tiles 1 and 2
+    pairs[30], pairs[2 * T + 30] = (COMP, 7), (REC, 7)      # the PUBCOMP first: tiles 0 and 2
+    pairs[-1] = (ACK, 8)
+    add(({}, row([[5, M, 2, 50], [6, M, 2, 60], [7, M, 2, 70], [8, M, 1, 80]], w, at=[2, 5, w // 2 + 1, w - 1]), acks(pairs)))
+    fill_to(3 * T)
+    add(({}, row([[1, M, 1, 1]], w), []))
+    add(({}, row([], w), []))
+    add(mixed_list(70, seed=71, w=w))  # starts at 3 T
+    fill_to(4 * T - 10)
+    add((dict(flags=W.CONNECTED), row([[4, M, 1, 40]], w, at=[3]), acks([(ACK, 4), (REC, 4)] * 10)))  # not present, over 4 T
+    add((dict(flags=LIVE | W.PASS), row([[4, P, 2, 40]], w), acks([(COMP, 4)])))
+    add((None, None, acks([(ACK, 4), (COMP, 5), (REC, 6)])))
+    fill_to(5 * T)
+    add(mixed_list(T, seed=72, w=w))  # starts at 5 T, the next one at 6 T
+    fill_to(7 * T + 5)
+    add(({}, row([[2, P, 2, 2]], w), []))
+    add(({}, row([], w), []))
+    case = RunCase(sessions, w)
+    assert case.total == 7 * T + 5 and case.m > 100 and int(case.offsets[2]) > 2 * T
+    return case
+
+
 # ---- the record call ---------------------------------------------------------------------------
 
 class RecCase:
@@ -348,3 +390,36 @@ def rec_fuzz(seed=5, n_boxes=1500, w=16):
             ds = [(int(rng.integers(0, 256)), int(rng.integers(0, 256)), int(rng.integers(0, 65536))) for _ in range(n)]  # any bytes
         boxes.append((None if rng.random() < 0.02 else r, ds))
     return RecCase(boxes, w, refs=True)
+
+
+def strided_record(refs=False, w=16):
+    """7 T + 5 positions over more than 100 inboxes, for a grid capped below the 8 tiles and the
+    four groups of rows: one inbox over tiles 0, 1 and 2 that takes more sends than its row has
+    free slots; inboxes that start exactly at 3 T and 4 T; a full row; a subscriber beyond the
+    table; empty inboxes at the end."""
+    boxes, at = [], [0]
+
+    def add(r, ds):
+        boxes.append((r, ds))
+        at[0] += len(ds)
+
+    def fill_to(pos):
+        while at[0] < pos:
+            k = len(boxes)
+            n = min(pos - at[0], 20 + 11 * k % 37)
+            free = [j for j in range(w) if (j + k) % 3]
+            add(row([[700 + j, M if j % 2 else P, 1 + j % 2, k] for j in range(w) if (j + k) % 3 == 0], w,
+                    at=[j for j in range(w) if (j + k) % 3 == 0]), deliveries(n, min(n, len(free) - 3 + k % 6), 8000 + k, first_id=65530 - 7 * k))
+
+    add(*rec_filler(1, w))
+    add(row([[i, M, 1, i] for i in range(1, 7)], w, at=list(range(0, 12, 2))), deliveries(2 * T + 300, 40, 21, 65520))
+    fill_to(3 * T)
+    add(row([], w), deliveries(T, 9, 22))  # starts at 3 T, the next one at 4 T
+    add(row([[i + 1, M, 1, i] for i in range(w)], w), deliveries(8, 3, 23))
+    add(None, deliveries(6, 3, 24))
+    fill_to(7 * T + 5)
+    add(row([], w), [])
+    add(holes(w), [])
+    case = RecCase(boxes, w, refs)
+    assert case.total == 7 * T + 5 and case.m > 100 and int(case.offsets[2]) > 2 * T
+    return case

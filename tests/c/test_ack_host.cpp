@@ -349,6 +349,7 @@ void errors(emqx_ack* h) {
   CHECK(emqx_ack_set_tuning(h, "nope", 1) == EMQX_ENOTFOUND);
   CHECK(emqx_ack_set_tuning(h, "rematch", 2) == EMQX_EINVAL);
   CHECK(emqx_ack_set_tuning(h, "rematch", 1) == EMQX_OK);
+  CHECK(emqx_ack_set_tuning(h, "max_blocks", 2) == EMQX_OK && emqx_ack_set_tuning(h, "scan_chunk", 3) == EMQX_OK);
   emqx_ack_stats st{};
   st.size = sizeof(st);
   CHECK(emqx_ack_stats_get(h, &st) == EMQX_OK && st.size == sizeof(st) && st.rematch == 1 && st.scratch_bytes == 0);

@@ -164,6 +164,7 @@ int main() {
     CHECK(emqx_subopts_create(EMQX_DELIVER_HOST_ONLY, &h) == EMQX_OK && h);
     CHECK(emqx_subopts_set_tuning(h, "max_load_pct", pct) == EMQX_OK);
     CHECK(emqx_subopts_set_tuning(h, "nope", 1) == EMQX_ENOTFOUND);
+    CHECK(emqx_subopts_set_tuning(h, "max_blocks", 2) == EMQX_OK && emqx_subopts_set_tuning(h, "scan_chunk", 3) == EMQX_OK);
     Rng r{static_cast<uint64_t>(pct) * 977};
     Table t;
     std::vector<uint32_t> f, s, ids;

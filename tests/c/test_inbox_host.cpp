@@ -216,6 +216,7 @@ int main() {
     s.size = sizeof(s);
     CHECK(emqx_inbox_stats_get(h, &s) == EMQX_OK && s.size == sizeof(s) && s.calls > 100 && s.last_passes >= 1);
     CHECK(emqx_inbox_set_tuning(h, "path", 1) == EMQX_OK && emqx_inbox_set_tuning(h, "nope", 1) == EMQX_ENOTFOUND);
+    CHECK(emqx_inbox_set_tuning(h, "max_blocks", 2) == EMQX_OK && emqx_inbox_set_tuning(h, "scan_chunk", 3) == EMQX_OK);
   }
   CHECK(emqx_inbox_destroy(h) == EMQX_OK);
   CHECK(emqx_inbox_destroy(nullptr) == EMQX_EINVAL);

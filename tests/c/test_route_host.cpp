@@ -173,6 +173,7 @@ int main() {
   CHECK(emqx_routetab_create(EMQX_ROUTE_HOST_ONLY, EMQX_ROUTE_MAX_NODES, &h) == EMQX_EINVAL);
   CHECK(emqx_routetab_create(EMQX_ROUTE_HOST_ONLY, LOCAL, &h) == EMQX_OK && h);
   CHECK(emqx_routetab_set_tuning(h, "max_blocks", 7) == EMQX_OK && emqx_routetab_set_tuning(h, "path", 1) == EMQX_OK);
+  CHECK(emqx_routetab_set_tuning(h, "scan_chunk", 3) == EMQX_OK);
   CHECK(emqx_routetab_set_tuning(h, "nope", 1) == EMQX_ENOTFOUND);
   Rng r{4242};
   Bag bag;

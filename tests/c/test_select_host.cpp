@@ -137,7 +137,7 @@ int main() {
   emqx_owntab* h = nullptr;
   CHECK(emqx_owntab_create(0, &h) == EMQX_EDEVICE && h == nullptr);  // this build has no device
   CHECK(emqx_owntab_create(EMQX_SELECT_HOST_ONLY, &h) == EMQX_OK && h);
-  CHECK(emqx_owntab_set_tuning(h, "max_blocks", 7) == EMQX_OK);
+  CHECK(emqx_owntab_set_tuning(h, "max_blocks", 7) == EMQX_OK && emqx_owntab_set_tuning(h, "scan_chunk", 3) == EMQX_OK);
   CHECK(emqx_owntab_set_tuning(h, "nope", 1) == EMQX_ENOTFOUND);
   Rng r{977};
   Table t;

@@ -268,6 +268,7 @@ int main() {
     CHECK(emqx_window_stats_get(h, &s) == EMQX_OK && s.size == sizeof(s) && s.calls > 100 && s.cap_in == 0);
     CHECK(emqx_window_set_tuning(h, "path", 0) == EMQX_OK && emqx_window_set_tuning(h, "nope", 1) == EMQX_ENOTFOUND);
     CHECK(emqx_window_set_tuning(h, "path", 1) == EMQX_OK && emqx_window_set_tuning(h, "path", 2) == EMQX_EINVAL);
+    CHECK(emqx_window_set_tuning(h, "max_blocks", 2) == EMQX_OK && emqx_window_set_tuning(h, "scan_chunk", 3) == EMQX_OK);
   }
   CHECK(emqx_window_destroy(h) == EMQX_OK);
   CHECK(emqx_window_destroy(nullptr) == EMQX_EINVAL);

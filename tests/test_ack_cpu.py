@@ -446,6 +446,37 @@ def test_tuning_keys(A):
         assert e.value.code == EINVAL
     h.set_tuning("rematch", 1)
     assert h.stats()["rematch"] == 1
+    case, rec = C.RUNS["list_of_65"](), C.RECORDS["free_0_2_5_takes_3"]()
+
+    def both():  # the host evaluator has no grid and no scan
+        table, slots, rows = case.table.copy(), case.slots.copy(), rec.slots.copy()
+        ran = h.run_host(case.subs, case.offsets, case.acks, table, slots, update_table=True)
+        recorded = h.record_host(rec.subs, rec.offsets, rec.opts, rec.verdicts, rec.pkt_ids, rows, refs=rec.refs)
+        C.check_run(case.reference(True), ran, slots, table)
+        C.check_rec(rec.reference(), recorded, rows)
+        return ran, recorded, table.tobytes(), slots.tobytes(), rows.tobytes()
+
+    before = both()
+    _grid_keys(h, 4096)
+    after = both()
+    C.same_run(after[0], before[0])
+    assert after[1].summary == before[1].summary and after[1].unrecorded.tobytes() == before[1].unrecorded.tobytes()
+    assert after[2:] == before[2:]
+
+
+def _grid_keys(h, max_blocks):
+    """"max_blocks" and "scan_chunk" on a host-only handle: accepted at 1 and at the maximum (it has
+    no grid to cap), EINVAL at 0, below it and above the maximum."""
+    from emqx_amd import _lib
+    for key, top in (("max_blocks", max_blocks), ("scan_chunk", 1024)):
+        for v in (1, top):
+            h.set_tuning(key, v)
+        for v in (0, -1, top + 1):
+            with pytest.raises(_lib.EngineError) as e:
+                h.set_tuning(key, v)
+            assert e.value.code == EINVAL
+    h.set_tuning("max_blocks", 1)
+    h.set_tuning("scan_chunk", 1)
 
 
 def test_stats_struct_is_versioned_by_size(A):

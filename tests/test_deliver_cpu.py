@@ -256,6 +256,29 @@ def test_tuning_keys(D):
         with pytest.raises(_lib.EngineError) as e:
             t.set_tuning("max_load_pct", v)
         assert e.value.code == EINVAL
+    case = C.shape("257", "mixed")
+    case.load(t)
+    before = t.enrich_host(*case.batch, compact=True)
+    _grid_keys(t, 16384)
+    after = t.enrich_host(*case.batch, compact=True)  # the host evaluator has no grid and no scan
+    C.check(case, after, True)
+    assert after.opts.tobytes() == before.opts.tobytes() and after.summary == before.summary
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(after.kept, before.kept))
+
+
+def _grid_keys(h, max_blocks):
+    """"max_blocks" and "scan_chunk" on a host-only handle: accepted at 1 and at the maximum (it has
+    no grid to cap), EINVAL at 0, below it and above the maximum."""
+    from emqx_amd import _lib
+    for key, top in (("max_blocks", max_blocks), ("scan_chunk", 1024)):
+        for v in (1, top):
+            h.set_tuning(key, v)
+        for v in (0, -1, top + 1):
+            with pytest.raises(_lib.EngineError) as e:
+                h.set_tuning(key, v)
+            assert e.value.code == EINVAL
+    h.set_tuning("max_blocks", 1)
+    h.set_tuning("scan_chunk", 1)
 
 
 def test_stats_struct_is_versioned_by_size(D):

@@ -1,5 +1,5 @@
 """The ack stage on the device (include/emqx_ack.h): every case of both calls through the three
-device entry points, every output byte, the rows, the table and the summary exact against the
+device entry points, with the grid at its default and capped at 2 blocks, every output byte, the rows, the table and the summary exact against the
 sequential restatement (tests/ack_ref.py) and identical to the host evaluator; nothing written past
 the defined extents; the refusals; scratch reuse; the chain window -> record -> inbox-stage
 grouping of raw acks -> ack -> window on one stream with no host read."""
@@ -34,11 +34,16 @@ def A():
     return ack
 
 
-@pytest.fixture(scope="module", params=[0, 1], ids=["carry_slot", "rematch"])
+@pytest.fixture(scope="module", params=[(0, None), (1, None), (0, 2), (1, 2)],
+                ids=["carry_slot", "rematch", "carry_slot-2_blocks", "rematch-2_blocks"])
 def handle(A, request):
-    """One handle a setting for the whole module: every test also reuses the scratch of the one before."""
+    """One handle a setting for the whole module: every test also reuses the scratch of the one
+    before.  Capped at 2 blocks, a block takes several tiles and groups of rows of every case."""
+    rematch, max_blocks = request.param
     h = A.Ack(0)
-    h.set_tuning("rematch", request.param)
+    h.set_tuning("rematch", rematch)
+    if max_blocks is not None:
+        h.set_tuning("max_blocks", max_blocks)
     return h
 
 

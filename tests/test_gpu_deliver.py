@@ -1,8 +1,10 @@
 """The enrich stage behind the fan-out on the device (include/emqx_deliver.h): every entry
-point against the restatement (tests/deliver_ref.py) and against the host evaluator, the tile
+point, with the grid at its default and capped at 2 blocks, against the restatement
+(tests/deliver_ref.py) and against the host evaluator, the tile
 and wave boundaries of the compaction, overflow and refusal, snapshot lifetime across a commit,
 and the match -> fan-out -> enrich chain on one stream."""
 
+import inspect
 import os
 import subprocess
 
@@ -30,6 +32,21 @@ def D():
     torch.cuda.set_device(0)
     from emqx_amd import deliver
     return deliver
+
+
+def table_maker(D, max_blocks=None):
+    def make():
+        t = D.SubOpts(0)
+        if max_blocks is not None:
+            t.set_tuning("max_blocks", max_blocks)
+        return t
+    return make
+
+
+@pytest.fixture
+def table(D):
+    """A maker of empty tables with the grid at its default (TestCappedAt2Blocks: capped)."""
+    return table_maker(D)
 
 
 def dev(a, dtype):
@@ -109,29 +126,29 @@ def all_forms(D, t, case):
             assert got.opts.tolist() == host.opts.tolist() and got.summary == host.summary
 
 
-def test_truth_table(D):
+def test_truth_table(D, table):
     case = C.truth_table()
-    all_forms(D, case.load(D.SubOpts(0)), case)
+    all_forms(D, case.load(table()), case)
 
 
 @pytest.mark.parametrize("name, mode", C.SHAPE_CASES)
-def test_shapes(D, name, mode):
+def test_shapes(D, table, name, mode):
     """0 deliveries (n = 0 and n = 3), 1, the wave (63 / 64 / 65) and tile (255 / 256 / 257)
     boundaries, and a 10 000-delivery message between empty ones over 40 tiles; mixed,
     all-dropped and none-dropped."""
     case = C.shape(name, mode)
-    all_forms(D, case.load(D.SubOpts(0)), case)
+    all_forms(D, case.load(table()), case)
 
 
 FUZZ_DROPPED = 21433  # of 146858: what the restatement drops, fixed so a degenerate generator cannot pass
 
 
 @pytest.mark.parametrize("pct", [50, 90])
-def test_fuzz(D, pct):
+def test_fuzz(D, table, pct):
     case = C.fuzz()
     s = case.reference()["summary"]
     assert s[1] == 146858 and s[3] == FUZZ_DROPPED and 0.05 < s[3] / s[1] < 0.60
-    t = D.SubOpts(0)
+    t = table()
     t.set_tuning("max_load_pct", pct)
     case.load(t)
     st = t.stats()
@@ -140,11 +157,11 @@ def test_fuzz(D, pct):
 
 
 @pytest.mark.parametrize("form", ["packed", "sync", "async"])
-def test_kept_overflow(D, form):
+def test_kept_overflow(D, table, form):
     """cap_kept one short: summary bit 0, complete kept_offsets, the kept arrays untouched."""
     from emqx_amd import _lib
     case = C.shape("257", "mixed")
-    t = case.load(D.SubOpts(0))
+    t = case.load(table())
     ref = case.reference()
     kept = ref["summary"][2]
     if form == "packed":
@@ -173,12 +190,12 @@ def test_kept_overflow(D, form):
 
 
 @pytest.mark.parametrize("form", ["sync", "async"])
-def test_input_refused(D, form):
+def test_input_refused(D, table, form):
     """offsets[n] > cap_in (the fan-out in front overflowed): summary bit 1, nothing else written."""
     from emqx_amd import _lib
     import torch
     case = C.shape("257", "mixed")
-    t = case.load(D.SubOpts(0))
+    t = case.load(table())
     b = DeviceBatch(D, case, True, cap_in=256)
     if form == "sync":
         with pytest.raises(_lib.EngineError) as e:
@@ -197,12 +214,12 @@ def test_input_refused(D, form):
     assert (b.koff.cpu().numpy().view(np.uint64) == 0x5A5A5A5A5A5A5A5A).all()
 
 
-def test_wild_device_offsets_stay_in_bounds(D):
+def test_wild_device_offsets_stay_in_bounds(D, table):
     """Offsets that decrease and exceed the count (only their last entry is within cap_in): the
     call completes, and nothing outside the first offsets[n] deliveries is written."""
     import torch
     case = C.shape("257", "mixed")
-    t = case.load(D.SubOpts(0))
+    t = case.load(table())
     b = DeviceBatch(D, case, True)
     b.ins[0].copy_(dev([0, 900, 5, 1 << 40, 2, 200], np.uint64))
     t.enrich_device_async(b.args, b.summary.data_ptr())
@@ -213,10 +230,10 @@ def test_wild_device_offsets_stay_in_bounds(D):
     assert (b.opts[:200].cpu().numpy() != SENTINEL).all()
 
 
-def test_async_call_keeps_its_snapshot_across_a_commit(D):
+def test_async_call_keeps_its_snapshot_across_a_commit(D, table):
     import torch
     case = C.fuzz()
-    t = case.load(D.SubOpts(0))
+    t = case.load(table())
     stream = torch.cuda.Stream(device=DEV)
     calls = [DeviceBatch(D, case, True) for _ in range(3)]
     stream.wait_stream(torch.cuda.current_stream())
@@ -235,6 +252,21 @@ def test_async_call_keeps_its_snapshot_across_a_commit(D):
     C.check(after, got, True)
     assert got.summary["no_subopts"] > case.reference()["summary"][4]
     assert t.stats()["n_entries"] == len(case.entries) - len(half)
+
+
+class TestCappedAt2Blocks:
+    """Every test above that builds its table with `table`, again with the grid capped at 2
+    blocks: a block takes several tiles of every case with more than 512 deliveries (20 of the 40
+    tiles of "10002", 287 of the fuzz batch's).  The tests above keep their ids."""
+
+    @pytest.fixture
+    def table(self, D):
+        return table_maker(D, max_blocks=2)
+
+
+for _name, _test in list(globals().items()):
+    if _name.startswith("test_") and "table" in inspect.signature(_test).parameters:
+        setattr(TestCappedAt2Blocks, _name, staticmethod(_test))
 
 
 def _broker_pair():

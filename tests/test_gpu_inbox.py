@@ -1,9 +1,10 @@
 """The inbox stage on the device (include/emqx_inbox.h): every named case through every entry
-point and both paths, every output array and the summary exact against the restatement
-(tests/inbox_ref.py) and byte-identical to the host evaluator; nothing written past the defined
-extents; the refusals; scratch reuse on one handle; the match -> fan-out -> enrich -> inbox chain
+point and both paths, with the grid at its default and capped at 2 blocks, every output array and
+the summary exact against the restatement (tests/inbox_ref.py) and byte-identical to the host
+evaluator; nothing written past the defined extents; the refusals; scratch reuse on one handle; the match -> fan-out -> enrich -> inbox chain
 on one stream."""
 
+import inspect
 import os
 import subprocess
 
@@ -35,14 +36,21 @@ def I():  # noqa: E743
     return inbox
 
 
-@pytest.fixture(scope="module")
-def handles(I):
-    """One handle a path for the whole module: every test also reuses the scratch of the one before."""
+def make_handles(I, max_blocks=None):
     hs = {}
     for path in PATHS:
         hs[path] = I.Inbox(0)
         hs[path].set_tuning("path", path)
+        if max_blocks is not None:
+            hs[path].set_tuning("max_blocks", max_blocks)
     return hs
+
+
+@pytest.fixture(scope="module")
+def handles(I):
+    """One handle a path for the whole module: every test also reuses the scratch of the one
+    before.  The grid is at its default (TestCappedAt2Blocks: capped)."""
+    return make_handles(I)
 
 
 def dev(a, dtype):
@@ -271,6 +279,22 @@ def test_box_overflow(I, handles, cap, path):
         code, summary = _summary_of(I, h, b, form)
         assert code in (None, _lib.EMQX_EOVERFLOW)
         C.check(ref, b.result(I, summary))
+
+
+class TestCappedAt2Blocks:
+    """Every test above that takes `handles`, again with the grid capped at 2 blocks: a block
+    takes several tiles of every case with more than 2 T deliveries and several rows of the
+    longest pass, the heads and path 1's prep and gather beyond 512.  The tests above keep their
+    ids."""
+
+    @pytest.fixture(scope="class")
+    def handles(self, I):
+        return make_handles(I, max_blocks=2)
+
+
+for _name, _test in list(globals().items()):
+    if _name.startswith("test_") and "handles" in inspect.signature(_test).parameters:
+        setattr(TestCappedAt2Blocks, _name, staticmethod(_test))
 
 
 def test_scratch_reuse_on_one_handle(I):

@@ -34,11 +34,16 @@ def W():
     return window
 
 
-@pytest.fixture(scope="module", params=[0, 1], ids=["tile_scan", "wave_per_inbox"])
+@pytest.fixture(scope="module", params=[(0, None), (1, None), (0, 2), (1, 2)],
+                ids=["tile_scan", "wave_per_inbox", "tile_scan-2_blocks", "wave_per_inbox-2_blocks"])
 def handle(W, request):
-    """One handle a path for the whole module: every test also reuses the scratch of the one before."""
+    """One handle a path for the whole module: every test also reuses the scratch of the one
+    before.  Capped at 2 blocks, a block takes several tiles and groups of inboxes of every case."""
+    path, max_blocks = request.param
     h = W.Window(0)
-    h.set_tuning("path", request.param)
+    h.set_tuning("path", path)
+    if max_blocks is not None:
+        h.set_tuning("max_blocks", max_blocks)
     return h
 
 
@@ -217,10 +222,13 @@ def test_refused_input_writes_only_the_summary(W, handle, form, what):
 
 
 def test_update_table_chains_two_batches_on_one_stream(W, handle):
+    chain_two_batches(W, handle, *C.chained())
+
+
+def chain_two_batches(W, handle, a, b):
     """Two asynchronous batches on one stream, the second reading the table the first wrote, no
     host read between them: equal to two sequential calls of the restatement."""
     import torch
-    a, b = C.chained()
     recs = C.records_of(a.table)
     ra = a.reference(update_table=True)
     R.run(a.subs, a.offsets, a.opts, recs, update_table=True)

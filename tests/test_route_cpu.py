@@ -46,6 +46,9 @@ def test_host_case(L, name):
     RC.check(case, got)
     again = t.route_host(case.offsets, case.filters)
     assert all(x.tobytes() == y.tobytes() for x, y in zip(got[:-1], again[:-1]))
+    t.set_tuning("scan_chunk", 1)  # a host-only table accepts it; the host evaluator has no scan
+    again = t.route_host(case.offsets, case.filters)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(got[:-1], again[:-1])) and again.summary == got.summary
     t.close()
 
 
@@ -162,6 +165,8 @@ def test_refusals(L):
     assert L.emqx_routetab_set_tuning(t._h, b"stored_mask", 1) == _lib.EMQX_OK
     assert L.emqx_routetab_set_tuning(t._h, b"path", 1) == _lib.EMQX_OK
     assert L.emqx_routetab_set_tuning(t._h, b"max_blocks", 2) == _lib.EMQX_OK
+    for v, rc in ((1, _lib.EMQX_OK), (1024, _lib.EMQX_OK), (0, _lib.EMQX_EINVAL), (-1, _lib.EMQX_EINVAL), (1025, _lib.EMQX_EINVAL)):
+        assert L.emqx_routetab_set_tuning(t._h, b"scan_chunk", v) == rc
     t.add([1, 2], [0, 63])
     t.commit()
 

@@ -241,6 +241,19 @@ def test_tuning_keys(S):
         with pytest.raises(_lib.EngineError) as e:
             t.set_tuning("max_blocks", v)
         assert e.value.code == EINVAL
+    case = C.shape("e257")
+    case.load(t)
+    before = t.select_host(*case.batch)
+    for v in (1, 1024):
+        t.set_tuning("scan_chunk", v)
+    for v in (0, -1, 1025):
+        with pytest.raises(_lib.EngineError) as e:
+            t.set_tuning("scan_chunk", v)
+        assert e.value.code == EINVAL
+    t.set_tuning("scan_chunk", 1)
+    after = t.select_host(*case.batch)  # the host evaluator has no scan
+    C.check(case, after)
+    assert after.rows() == before.rows() and after.summary == before.summary
 
 
 def test_stats_struct_is_versioned_by_size(S):

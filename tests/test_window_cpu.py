@@ -314,6 +314,27 @@ def test_tuning_keys(W):
         assert e.value.code == EINVAL
     h.set_tuning("path", 1)
     assert h.stats()["path"] == 1
+    case = C.LAYOUTS["total_3T+5"]()
+    before = h.run_host(case.subs, case.offsets, case.opts, case.table.copy())
+    _grid_keys(h, 2048)
+    after = h.run_host(case.subs, case.offsets, case.opts, case.table.copy())  # the host evaluator has no grid and no scan
+    C.check(case.reference(), after)
+    C.same(after, before)
+
+
+def _grid_keys(h, max_blocks):
+    """"max_blocks" and "scan_chunk" on a host-only handle: accepted at 1 and at the maximum (it has
+    no grid to cap), EINVAL at 0, below it and above the maximum."""
+    from emqx_amd import _lib
+    for key, top in (("max_blocks", max_blocks), ("scan_chunk", 1024)):
+        for v in (1, top):
+            h.set_tuning(key, v)
+        for v in (0, -1, top + 1):
+            with pytest.raises(_lib.EngineError) as e:
+                h.set_tuning(key, v)
+            assert e.value.code == EINVAL
+    h.set_tuning("max_blocks", 1)
+    h.set_tuning("scan_chunk", 1)
 
 
 def test_stats_struct_is_versioned_by_size(W):

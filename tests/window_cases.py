@@ -204,10 +204,53 @@ def fuzz(seed=7, total=6000):
     return Case(boxes)
 
 
+def strided(seed=0):
+    """7 T + 5 deliveries over about 1 000 inboxes, for a grid capped below the 8 tiles and the four
+    groups of 256 inboxes of the write-back: one inbox over tiles 0, 1 and 2 whose sends end in tile
+    1 and whose queue fills in tile 2, QoS 0 among them throughout, so that sends, QoS 0, queued and
+    evicting verdicts lie across the borders; an inbox that starts exactly at 3 T; inboxes without
+    deliveries at that border and at the end; a subscriber beyond the table."""
+    kinds = [dict(), dict(inflight_max=4, mq_max=3, mq_len=1), dict(flags=P | S0, mq_max=6), dict(flags=P, mq_max=5, mq_len=5),
+             dict(inflight_max=0, next_pkt_id=65533)]
+    boxes, at = [], [0]
+
+    def add(rec, o):
+        boxes.append((rec, o))
+        at[0] += len(o)
+
+    def fill_to(pos):
+        while at[0] < pos:
+            k = len(boxes)
+            n = min(pos - at[0], 1 + (5 * k + seed) % 19)
+            rec = dict(dict(inflight=k % 7, next_pkt_id=1 + 977 * k % 65535), **kinds[(k + seed) % len(kinds)])
+            add(session(**rec), mix(n - n // 4, n // 4, seed=seed + k))
+
+    add(*filler(5, 1 + seed))
+    add(session(inflight=3, inflight_max=T + 100, mq_max=T // 2, next_pkt_id=65000), mix(2 * T - 200, 500, seed=seed + 3))
+    fill_to(3 * T)
+    add(session(), [])
+    add(session(flags=P), [])
+    add(*filler(40, 2 + seed))  # starts at 3 T
+    add(None, mix(4, 3, 1, 1, seed=seed + 4))
+    fill_to(7 * T + 5)
+    add(session(), [])
+    case = Case(boxes)
+    assert case.total == 7 * T + 5 and case.m > 3 * 256 and int(case.offsets[2]) > 2 * T
+    return case
+
+
 def chained(seed=11):
     """Two batches over one table: the second's inboxes name subscribers of the first's table, most
     of them ones the first batch changed."""
-    a, b = fuzz(seed, 5000), fuzz(seed + 2, 3000)
+    return chain(fuzz(seed, 5000), fuzz(seed + 2, 3000), seed)
+
+
+def strided_chained(seed=21):
+    """Two batches of 7 T + 5 deliveries over one table, as chained()."""
+    return chain(strided(0), strided(5), seed)
+
+
+def chain(a, b, seed):
     rng = np.random.default_rng(seed + 1)
     named = rng.permutation(np.unique(a.subs[a.subs < a.sub_limit]))
     others = np.setdiff1d(np.arange(a.sub_limit, dtype=np.uint32), named)
