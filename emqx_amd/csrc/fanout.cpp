@@ -339,7 +339,10 @@ struct emqx_subtab {
   std::vector<std::unique_ptr<FoScratch>> scratch;  // one per stream that called
   uint64_t* h_total = nullptr;
   uint32_t seed = 0x2545F491u;
-  uint32_t rr_first0 = 0;  // emqx_subtab_set_tuning "rr_seed0"
+  // emqx_subtab_set_tuning's keys that an enqueue reads: set_tuning holds cmu, an enqueue mu, so
+  // the two may run at once; atomics (relaxed: a call takes the old value or the new one)
+  std::atomic<uint32_t> rr_first0{0};   // "rr_seed0"
+  std::atomic<uint32_t> max_blocks{0};  // "max_blocks" (0: unset)
   // commit statistics (emqx_subtab_commit_stats)
   uint64_t st_commits = 0, st_full = 0, st_words = 0, st_records = 0, st_moves = 0, st_last_kind = 0;
   double st_host_us = 0, st_total_us = 0;
@@ -1341,7 +1344,8 @@ int enqueue_fanout(emqx_subtab* s, uint32_t strategy, const uint64_t* d_moff, co
   a.strategy = strategy;
   s->seed = s->seed * 1664525u + 1013904223u;
   a.seed = s->seed;
-  a.rr_first0 = s->rr_first0;
+  a.rr_first0 = s->rr_first0.load(std::memory_order_relaxed);
+  a.max_blocks = s->max_blocks.load(std::memory_order_relaxed);
   a.entry_topic = c->entry_topic;
   a.csum = c->csum;
   a.gchunk = c->gchunk;
@@ -1930,7 +1934,10 @@ int emqx_subtab_set_tuning(emqx_subtab* s, const char* key, int64_t value) {
   } else if (!std::strcmp(key, "inject_bad_alloc")) {
     s->inject_bad_alloc = static_cast<uint32_t>(value);
   } else if (!std::strcmp(key, "rr_seed0")) {  // round_robin's first pick: member 0 (SURVEY §8 d)
-    s->rr_first0 = value ? 1u : 0u;
+    s->rr_first0.store(value ? 1u : 0u, std::memory_order_relaxed);
+  } else if (!std::strcmp(key, "max_blocks")) {  // read at enqueue
+    if (value < 1 || value > FO_BLOCKS) return EMQX_EINVAL;
+    s->max_blocks.store(static_cast<uint32_t>(value), std::memory_order_relaxed);
   } else {
     return EMQX_ENOTFOUND;
   }
@@ -2032,7 +2039,7 @@ int emqx_share_repick(emqx_subtab* s, uint32_t strategy, uint64_t n, const uint3
   a.strategy = strategy;
   s->seed = s->seed * 1664525u + 1013904223u;
   a.seed = s->seed;
-  a.rr_first0 = s->rr_first0;
+  a.rr_first0 = s->rr_first0.load(std::memory_order_relaxed);
   a.n = n;
   a.filter_ids = reinterpret_cast<const uint32_t*>(d + o_f);
   a.group_ids = reinterpret_cast<const uint32_t*>(d + o_g);

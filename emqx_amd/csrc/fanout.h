@@ -142,6 +142,8 @@ struct FanoutArgs {
   uint32_t seed;             // per-call seed of random picks
   uint32_t rr_first0;        // round_robin's first pick of a state entry is member 0 (SURVEY §8 d's
                              // "counter seeded 0"), not rand:uniform(N) (emqx_subtab "rr_seed0")
+  uint32_t max_blocks;       // emqx_subtab "max_blocks": 0 (unset), or 1..FO_BLOCKS: the block ranges the
+                             // entries are split over and the cap of every grid whose blocks stride
   uint32_t* entry_topic;     // [m] scratch: entry -> topic
   uint64_t* csum;            // [m_cap / FO_WCHUNK + 2] deliveries per chunk of FO_WCHUNK entries
   uint64_t* gchunk;          // [m_cap / FO_WCHUNK + 2] $share picks per chunk (round_robin / sticky)

@@ -121,8 +121,11 @@ __device__ __forceinline__ uint64_t fo_wave_sum(uint64_t v) {
 // its block's base.  (A one-pass decoupled look-back in the write kernel measured slower: its
 // chains of unpublished predecessors at the kernel's start, and the registers it held, cost
 // more than the count kernel, profiles/r4_v16_fanout_onepass_ab.txt.)
-__device__ __forceinline__ uint64_t fo_per_block(uint64_t m) {
-  return ((m + FO_BLOCKS - 1) / FO_BLOCKS + FO_WCHUNK - 1) & ~static_cast<uint64_t>(FO_WCHUNK - 1);
+// max_blocks (emqx_subtab "max_blocks", 0: unset) splits the entries over that many block ranges
+// instead of FO_BLOCKS; the count kernel's blocks past them get an empty range.
+__device__ __forceinline__ uint64_t fo_per_block(uint64_t m, uint32_t max_blocks) {
+  const uint64_t nb = max_blocks ? max_blocks : FO_BLOCKS;
+  return ((m + nb - 1) / nb + FO_WCHUNK - 1) & ~static_cast<uint64_t>(FO_WCHUNK - 1);
 }
 
 __global__ __launch_bounds__(FO_THREADS) void fanout_count_kernel(FanoutArgs a) {
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(FO_THREADS) void fanout_count_kernel(FanoutArgs a) 
   const bool stateful = fo_stateful(a.strategy);
   const uint32_t lane = fo_lane(), wv = threadIdx.x >> 6;
   constexpr uint32_t EU = FO_WCHUNK / 64;
-  const uint64_t m = fo_entries(a), per = fo_per_block(m);
+  const uint64_t m = fo_entries(a), per = fo_per_block(m, a.max_blocks);
   const uint64_t lo = min<uint64_t>(m, per * blockIdx.x), hi = min<uint64_t>(m, per * (blockIdx.x + 1));
   uint64_t sum = 0, gsum = 0;
   for (uint64_t c0 = lo + uint64_t(wv) * FO_WCHUNK; c0 < hi; c0 += uint64_t(FO_THREADS / 64) * FO_WCHUNK) {
@@ -295,7 +298,7 @@ __global__ __launch_bounds__(FO_THREADS, 5) void fanout_write_kernel(FanoutArgs 
   const bool stateful = fo_stateful(a.strategy);
   // over cap (deliveries or picks): offsets only, no ids, no pick state consumed
   const bool ids = !(a.ctl[FO_CTL_FLAGS] & (FO_SUM_F_OVERFLOW | FO_SUM_F_PICKS));
-  const uint64_t per = fo_per_block(m);
+  const uint64_t per = fo_per_block(m, a.max_blocks);
   const uint64_t nwaves = uint64_t(gridDim.x) * (FO_THREADS / 64);
   for (uint64_t e0 = (uint64_t(blockIdx.x) * (FO_THREADS / 64) + wv) * FO_WCHUNK; e0 < m;
        e0 += nwaves * FO_WCHUNK) {
@@ -899,9 +902,14 @@ uint32_t grid_for(uint64_t items, uint32_t per_block) {
   return static_cast<uint32_t>(g < 1 ? 1 : (g > 65536 ? 65536 : g));
 }
 
-uint32_t probe_blocks(uint64_t pk_cap) {
-  const uint32_t g = grid_for(pk_cap, FO_THREADS);
-  return g < FO_BLOCKS ? g : FO_BLOCKS;
+// The grid under the table's "max_blocks" (0: unset, the grid as it is).
+uint32_t fo_capped(const FanoutArgs& a, uint32_t grid) {
+  return a.max_blocks && grid > a.max_blocks ? a.max_blocks : grid;
+}
+
+uint32_t probe_blocks(const FanoutArgs& a) {
+  const uint32_t g = grid_for(a.pk_cap, FO_THREADS);
+  return fo_capped(a, g < FO_BLOCKS ? g : FO_BLOCKS);
 }
 
 // ---- incremental commits of the subscription table ----------------------------------------
@@ -993,14 +1001,15 @@ __global__ __launch_bounds__(256) void fanout_to_host_kernel(const uint64_t* d_o
 }  // namespace
 
 hipError_t launch_fanout(const FanoutArgs& a, uint64_t m_cap, hipStream_t s) {
-  hipLaunchKernelGGL(fanout_entry_topic_kernel, dim3(grid_for(a.n + 1, FO_THREADS)), dim3(FO_THREADS), 0, s, a);
+  hipLaunchKernelGGL(fanout_entry_topic_kernel, dim3(fo_capped(a, grid_for(a.n + 1, FO_THREADS))), dim3(FO_THREADS), 0,
+                     s, a);
   hipLaunchKernelGGL(fanout_count_kernel, dim3(FO_BLOCKS), dim3(FO_THREADS), 0, s, a);
   hipLaunchKernelGGL(fanout_partials_kernel, dim3(1), dim3(FO_BLOCKS), 0, s, a);
   // one wave per FO_WCHUNK entries up to m_cap (waves past m exit at once)
-  hipLaunchKernelGGL(fanout_write_kernel, dim3(grid_for(m_cap, FO_WCHUNK * (FO_THREADS / 64))), dim3(FO_THREADS), 0, s,
-                     a);
+  hipLaunchKernelGGL(fanout_write_kernel, dim3(fo_capped(a, grid_for(m_cap, FO_WCHUNK * (FO_THREADS / 64)))),
+                     dim3(FO_THREADS), 0, s, a);
   if (fo_stateful(a.strategy))
-    hipLaunchKernelGGL(fanout_pick_probe_kernel, dim3(probe_blocks(a.pk_cap)), dim3(FO_THREADS), 0, s, a);
+    hipLaunchKernelGGL(fanout_pick_probe_kernel, dim3(probe_blocks(a)), dim3(FO_THREADS), 0, s, a);
   else
     hipLaunchKernelGGL(fanout_finish_kernel, dim3(1), dim3(FO_THREADS), 0, s, a, 0u);
   return hipGetLastError();
@@ -1028,9 +1037,11 @@ uint64_t fanout_sort_temp_bytes(uint64_t pk_cap) {
 
 hipError_t launch_fanout_resolve(const FanoutArgs& a, void* sort_temp, uint64_t sort_temp_bytes, hipStream_t s) {
   if (a.run_cnt) {  // small path
-    hipLaunchKernelGGL(fanout_pick_classify_kernel, dim3(grid_for(a.pk_cap, FO_THREADS * 4)), dim3(FO_THREADS), 0, s, a);
-    hipLaunchKernelGGL(fanout_resolve_small_kernel, dim3(1 + grid_for(a.pk_cap, 1024)), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(fanout_finish_kernel, dim3(1), dim3(FO_THREADS), 0, s, a, probe_blocks(a.pk_cap));
+    hipLaunchKernelGGL(fanout_pick_classify_kernel, dim3(fo_capped(a, grid_for(a.pk_cap, FO_THREADS * 4))),
+                       dim3(FO_THREADS), 0, s, a);
+    // (block 0 sorts the multi-pick runs; the others stride over the runs of one pick)
+    hipLaunchKernelGGL(fanout_resolve_small_kernel, dim3(1 + fo_capped(a, grid_for(a.pk_cap, 1024))), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(fanout_finish_kernel, dim3(1), dim3(FO_THREADS), 0, s, a, probe_blocks(a));
     return hipGetLastError();
   }
   // large path: stable by run: each run keeps output (message) order; the pad sorts last
@@ -1039,10 +1050,10 @@ hipError_t launch_fanout_resolve(const FanoutArgs& a, void* sort_temp, uint64_t 
                                                            a.pk_svals, static_cast<size_t>(a.pk_cap), 0u,
                                                            pick_key_bits(a.pk_cap), s);
   if (e != hipSuccess) return e;
-  const uint32_t grid = grid_for(a.pk_cap, FO_THREADS * 4);
+  const uint32_t grid = fo_capped(a, grid_for(a.pk_cap, FO_THREADS * 4));
   hipLaunchKernelGGL(fanout_resolve_heads_kernel, dim3(grid), dim3(FO_THREADS), 0, s, a);
   hipLaunchKernelGGL(fanout_resolve_apply_kernel, dim3(grid), dim3(FO_THREADS), 0, s, a);
-  hipLaunchKernelGGL(fanout_finish_kernel, dim3(1), dim3(FO_THREADS), 0, s, a, probe_blocks(a.pk_cap));
+  hipLaunchKernelGGL(fanout_finish_kernel, dim3(1), dim3(FO_THREADS), 0, s, a, probe_blocks(a));
   return hipGetLastError();
 }
 

@@ -101,7 +101,11 @@ class SubTable:
         return int(_lib.lib().emqx_subtab_commit_wait(self._h))
 
     def set_tuning(self, key: str, value: int) -> None:
-        """emqx_subtab_set_tuning (fault injection for tests)."""
+        """emqx_subtab_set_tuning: fault injection for tests ("inject_drain_error",
+        "inject_bad_alloc"); "rr_seed0" = 1: round_robin's first pick of a state entry is member 0;
+        "max_blocks" (1..1024, read at enqueue): the fan-out's entries are split over this many
+        block ranges instead of 1024 and every strided fan-out grid is capped at it (same results;
+        tests set it to run several chunks per block and the strided loops at small sizes)."""
         check(_lib.lib().emqx_subtab_set_tuning(self._h, key.encode(), int(value)), "emqx_subtab_set_tuning")
 
     def stats(self) -> dict:

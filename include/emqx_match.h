@@ -297,6 +297,11 @@ int emqx_subtab_commit_wait(emqx_subtab* s);
  * their host allocations (the call returns EMQX_ENOMEM).  "rr_seed0" = 1: round_robin's first pick
  * of a (group, publisher) state entry is the first member instead of rand:uniform(N) (SURVEY §8 d's
  * config E: "round_robin with counter seeded 0"; deterministic, so checked pick by pick).
+ * "max_blocks" (1..1024, unset by default; EMQX_EINVAL outside the range; read at enqueue): the
+ * fan-out splits a call's match entries over this many block ranges instead of 1024, and every
+ * fan-out grid whose blocks stride is capped at it (tests set it so that a block range holds
+ * several 256-entry chunks and the strided loops run at a few thousand entries; the results are
+ * the same).  Unset, the split and every grid are the defaults.
  * EMQX_ENOTFOUND for unknown keys. */
 int emqx_subtab_set_tuning(emqx_subtab* s, const char* key, int64_t value);
 /* counts[0..3] = live plain subscriptions, live shared memberships, groups with members,
