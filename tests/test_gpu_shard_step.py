@@ -9,6 +9,13 @@ driven by emqx_amd/dist.py ShardedMatcher.match_all), ID-for-ID against the orac
   before the answer exchange;
 * two ranks sharing the one GPU over gloo (a rehearsal of the N-rank exchange on real device
   kernels), each rank's own batch checked ID-for-ID.
+
+These runs stop at world 8 and a few thousand topics a rank: the sort's (bucket, tile) table has
+at most 600 entries, so the segmented scan never runs here.  tests/test_gpu_shard_world.py drives
+the step's C API directly (tests/shard_cases.py, against tests/shard_ref.py and host mode) at
+world 64, on both sides of kOneBlockScan = 8,192 table entries (42 and 43 tiles at world 64, five
+exact segments at world 5, 405 segments for 1.1 M topics), through the second trips of the recv,
+answer, gather and merge loops, and through the fixed form's flags at world 3 and 64.
 """
 
 import os
