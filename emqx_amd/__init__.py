@@ -16,6 +16,8 @@ Modules mirror the reference's Erlang modules on the hot path:
                           mqueue admission of every inbox: packet ids, what is queued, what is dropped)
   :mod:`emqx_amd.ack`     emqx_session puback/2 + pubrec/2 + pubcomp/2 + batch_n/1 over emqx_inflight (which packet ids
                           are inflight per session; a batch of acks against them: reason codes, refs, the freed window)
+  :mod:`emqx_amd.retry`   emqx_session retry/1 + replay/1, emqx_message is_expired/1 (when each inflight entry went in:
+                          redelivery lists in timestamp order, expired messages dropped, the next retry timer)
   :mod:`emqx_amd.route`   emqx_broker aggre/1 + route/2 + do_route/2, emqx_router_helper cleanup_routes/1 (the route
                           bag in device memory: routes per message, forward lists per node, the local CSR)
   :mod:`emqx_amd.dist`    multi-GPU: replicated tables + data-parallel topic split,
@@ -30,4 +32,5 @@ from .select import HookIndex, OwnerTable  # noqa: F401,E402  (hook consumers se
 from .inbox import Inbox  # noqa: F401,E402  (a batch's deliveries grouped by subscriber)
 from .window import Window  # noqa: F401,E402  (inflight and mqueue admission per inbox)
 from .ack import Ack  # noqa: F401,E402  (inflight slots and PUBACK / PUBREC / PUBCOMP per session)
+from .retry import Retry  # noqa: F401,E402  (inflight ages, redelivery lists and timers per session)
 from .route import ClusterRouter, RouteTable  # noqa: F401,E402  (dests, aggre/1 and forward lists per node)

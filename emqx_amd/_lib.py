@@ -104,6 +104,12 @@ ACK_EXPORTS = (
     "emqx_ack_record_batch_device_async", "emqx_ack_record_host", "emqx_ack_run_batch", "emqx_ack_run_batch_device",
     "emqx_ack_run_batch_device_async", "emqx_ack_run_host", "emqx_ack_set_tuning", "emqx_ack_stats_get",
 )
+# Every symbol include/emqx_retry.h declares (inflight ages, redelivery lists and timers per session).
+RETRY_EXPORTS = (
+    "emqx_retry_create", "emqx_retry_destroy", "emqx_retry_reserve", "emqx_retry_stamp_batch", "emqx_retry_stamp_batch_device",
+    "emqx_retry_stamp_batch_device_async", "emqx_retry_stamp_host", "emqx_retry_sweep_batch", "emqx_retry_sweep_batch_device",
+    "emqx_retry_sweep_batch_device_async", "emqx_retry_sweep_host", "emqx_retry_set_tuning", "emqx_retry_stats_get",
+)
 # Every symbol include/emqx_route.h declares (dests, aggre/1 and forward lists per node).
 ROUTE_EXPORTS = (
     "emqx_routetab_create", "emqx_routetab_destroy", "emqx_routetab_add", "emqx_routetab_remove",
@@ -350,6 +356,43 @@ class AckStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
 
 
+class RetryStampArgs(ctypes.Structure):
+    """struct emqx_retry_stamp_args (include/emqx_retry.h): the buffers of one stamp call."""
+    _fields_ = [
+        ("subs", ctypes.c_void_p), ("n_boxes", ctypes.c_void_p), ("m", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("slots", ctypes.c_void_p), ("stamps", ctypes.c_void_p), ("w", ctypes.c_uint64), ("sub_limit", ctypes.c_uint64),
+        ("now_ms", ctypes.c_uint64),
+    ]
+
+
+class RetrySweepArgs(ctypes.Structure):
+    """struct emqx_retry_sweep_args (include/emqx_retry.h): the buffers of one sweep call."""
+    _fields_ = [
+        ("subs", ctypes.c_void_p), ("n_boxes", ctypes.c_void_p), ("m", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("update_table", ctypes.c_uint64),
+        ("slots", ctypes.c_void_p), ("stamps", ctypes.c_void_p), ("w", ctypes.c_uint64),
+        ("now_ms", ctypes.c_uint64), ("interval_ms", ctypes.c_uint64), ("intervals", ctypes.c_void_p),
+        ("deadlines", ctypes.c_void_p), ("ref_limit", ctypes.c_uint64), ("mode", ctypes.c_uint64), ("cap_out", ctypes.c_uint64),
+        ("out_offsets", ctypes.c_void_p), ("out_items", ctypes.c_void_p), ("out_status", ctypes.c_void_p),
+        ("out_counts", ctypes.c_void_p), ("out_timers", ctypes.c_void_p),
+    ]
+
+
+class RetryStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_boxes", ctypes.c_uint64), ("w", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("calls", ctypes.c_uint64),
+        ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
 class RouteBatch(ctypes.Structure):
     """struct emqx_route_batch (include/emqx_route.h): the buffers of one route call."""
     _fields_ = [
@@ -561,6 +604,19 @@ def lib():
         "emqx_ack_run_host": (i32, [vp, ctypes.POINTER(AckRunArgs), vp]),
         "emqx_ack_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_ack_stats_get": (i32, [vp, ctypes.POINTER(AckStats)]),
+        "emqx_retry_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_retry_destroy": (i32, [vp]),
+        "emqx_retry_reserve": (i32, [vp, u64, u64]),
+        "emqx_retry_stamp_batch": (i32, [vp, ctypes.POINTER(RetryStampArgs), vp]),
+        "emqx_retry_stamp_batch_device": (i32, [vp, ctypes.POINTER(RetryStampArgs), vp, vp]),
+        "emqx_retry_stamp_batch_device_async": (i32, [vp, ctypes.POINTER(RetryStampArgs), vp, vp]),
+        "emqx_retry_stamp_host": (i32, [vp, ctypes.POINTER(RetryStampArgs), vp]),
+        "emqx_retry_sweep_batch": (i32, [vp, ctypes.POINTER(RetrySweepArgs), vp]),
+        "emqx_retry_sweep_batch_device": (i32, [vp, ctypes.POINTER(RetrySweepArgs), vp, vp]),
+        "emqx_retry_sweep_batch_device_async": (i32, [vp, ctypes.POINTER(RetrySweepArgs), vp, vp]),
+        "emqx_retry_sweep_host": (i32, [vp, ctypes.POINTER(RetrySweepArgs), vp]),
+        "emqx_retry_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_retry_stats_get": (i32, [vp, ctypes.POINTER(RetryStats)]),
         "emqx_routetab_create": (i32, [ctypes.c_int32, u32, ctypes.POINTER(vp)]),
         "emqx_routetab_destroy": (i32, [vp]),
         "emqx_routetab_add": (i32, [vp, vp, vp, vp, u64]),

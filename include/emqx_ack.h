@@ -73,9 +73,10 @@
  *
  * Out of scope, kept by the caller: the mqueue's contents and emqx_mqueue:out/1 (the stage gives
  * `room`; the caller pops that many non-QoS-0 messages and feeds them to the window stage as an
- * inbox: dequeue/1 ends in the same deliver/3 fold), message expiry, retry/1 and the timestamps,
- * replay/1, awaiting_rel and the inbound QoS 2 path (publish/3, pubrel/2), latency stats, a NIF
- * binding.
+ * inbox: dequeue/1 ends in the same deliver/3 fold), awaiting_rel and the inbound QoS 2 path
+ * (publish/3, pubrel/2), latency stats, a NIF binding.  The timestamps of the entries, retry/1 with
+ * message expiry and replay/1 are the retry stage's (emqx_retry.h): it keeps a stamp per slot next
+ * to slots[] and is called behind every record and run call.
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_inbox.h: the
  * calls on one handle share its device scratch and are ordered by the handle.
