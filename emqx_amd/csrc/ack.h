@@ -10,6 +10,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "stage_common.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define AK_HD __host__ __device__
@@ -115,25 +117,6 @@ AK_HD inline uint32_t ak_nth_set(uint64_t mask, uint32_t r) {
 }
 
 AK_HD inline uint64_t ak_tiles(uint64_t total) { return (total + AK_TILE - 1) / AK_TILE; }
-
-// The first k in [lo, hi) with offsets[k] >= x, or > x (hi when there is none).  At most 64
-// halvings whatever the offsets hold, every index read lies in [lo, hi).
-AK_HD inline uint64_t ak_lower(const uint64_t* offsets, uint64_t lo, uint64_t hi, uint64_t x) {
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-AK_HD inline uint64_t ak_upper(const uint64_t* offsets, uint64_t lo, uint64_t hi, uint64_t x) {
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 #if defined(__HIPCC__)
 // Arguments of the device passes of a record call; the first block is emqx_ack_record_args'.

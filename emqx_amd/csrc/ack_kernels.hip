@@ -58,57 +58,14 @@ __device__ inline uint64_t ak_tiles_eff(uint64_t total) {  // a call without pos
   return t ? t : 1;
 }
 
-// Exclusive scan of x over the block; *all: the block's sum.  Two barriers.
-__device__ inline uint32_t ak_block_scan(uint32_t x, uint32_t* wsum, uint32_t* all) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t incl = x;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  __syncthreads();  // the readers of the scan before this one are done
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0, sum = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < AK_WAVES; ++w) {
-    if (w < wave) before += wsum[w];
-    sum += wsum[w];
-  }
-  *all = sum;
-  return before + incl - x;
-}
-
-// The block's sums of N per-thread values into ctr[word0 ..], and flag bits into ctr[AK_S_FLAGS].
-// Every thread of the block calls it.
-template <uint32_t N>
-__device__ inline void ak_report(unsigned long long* ctr, uint32_t word0, const uint64_t (&v)[N], uint32_t flags) {
-  __shared__ unsigned long long red[N];
-  __shared__ uint32_t red_flags;
-  if (threadIdx.x < N) red[threadIdx.x] = 0;
-  if (threadIdx.x == 0) red_flags = 0;
-  __syncthreads();
-#pragma unroll
-  for (uint32_t c = 0; c < N; ++c) {
-    uint64_t s = v[c];
-    for (uint32_t d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&red[c], static_cast<unsigned long long>(s));
-  }
-  if (flags) atomicOr(&red_flags, flags);
-  __syncthreads();
-  if (threadIdx.x < N && red[threadIdx.x]) atomicAdd(ctr + word0 + threadIdx.x, red[threadIdx.x]);
-  if (threadIdx.x == N && red_flags) atomicOr(ctr + AK_S_FLAGS, static_cast<unsigned long long>(red_flags));
-}
-
-// The inboxes a tile's positions can belong to, as bounds of ak_upper: thread 0 and 1 search the
+// The inboxes a tile's positions can belong to, as bounds of csr_upper: thread 0 and 1 search the
 // whole array once a tile.  ext[0] <= ext[1] <= m + 1.
 __device__ inline void ak_tile_extent(const uint64_t* offsets, uint64_t m, uint64_t ts, uint64_t total, uint64_t* ext) {
   __syncthreads();  // the readers of the tile before are done
-  if (threadIdx.x == 0) ext[0] = ak_upper(offsets, 0, m + 1, ts);
+  if (threadIdx.x == 0) ext[0] = csr_upper(offsets, 0, m + 1, ts);
   if (threadIdx.x == 1) {
     const uint64_t end = total - ts < AK_TILE ? total : ts + AK_TILE;  // (ts < total)
-    ext[1] = ak_upper(offsets, 0, m + 1, end - 1);
+    ext[1] = csr_upper(offsets, 0, m + 1, end - 1);
   }
   __syncthreads();
 }
@@ -118,7 +75,7 @@ __device__ inline void ak_tile_extent(const uint64_t* offsets, uint64_t m, uint6
 __device__ inline uint64_t ak_box_of(const uint64_t* offsets, uint64_t m, const uint64_t* ext, uint64_t d, uint64_t k_at) {
   if (k_at < m && offsets[k_at] <= d && d < offsets[k_at + 1]) return k_at;
   const uint64_t lo = ext[0], hi = ext[1] < lo ? lo : ext[1];
-  const uint64_t u = ak_upper(offsets, lo, hi, d);
+  const uint64_t u = csr_upper(offsets, lo, hi, d);
   return (u >= 1 && u <= m) ? u - 1 : AK_NONE;
 }
 
@@ -163,7 +120,7 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_rec_heads_kernel(AkRecArgs a) {
     const bool last = tile + 1 == tiles;
     const uint32_t bits = ak_load_sends(a.verdicts, ts + static_cast<uint64_t>(threadIdx.x) * AK_ROWS, total);
     uint32_t all;
-    uint32_t run = ak_block_scan(static_cast<uint32_t>(__popc(bits)), wsum, &all);
+    uint32_t run = block_excl_scan<AK_BLOCK>(static_cast<uint32_t>(__popc(bits)), wsum, &all);
 #pragma unroll
     for (uint32_t j = 0; j < AK_ROWS; ++j) {
       pre[threadIdx.x * AK_ROWS + j] = run;
@@ -176,8 +133,8 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_rec_heads_kernel(AkRecArgs a) {
     __syncthreads();
     // the inboxes whose head lies in [ts, ts + AK_TILE); the last tile also takes the heads at its
     // end (inboxes without deliveries behind the last delivery, and inbox_offsets[m] itself)
-    const uint64_t k_lo = ak_lower(a.inbox_offsets, 0, m + 1, ts);
-    const uint64_t k_hi = last ? m + 1 : ak_lower(a.inbox_offsets, 0, m + 1, ts + AK_TILE);
+    const uint64_t k_lo = csr_lower(a.inbox_offsets, 0, m + 1, ts);
+    const uint64_t k_hi = last ? m + 1 : csr_lower(a.inbox_offsets, 0, m + 1, ts + AK_TILE);
     for (uint64_t k = k_lo + threadIdx.x; k < k_hi; k += AK_BLOCK) {
       const uint64_t off = a.inbox_offsets[k];
       const uint64_t p = off < total ? off : total;
@@ -187,37 +144,15 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_rec_heads_kernel(AkRecArgs a) {
   }
 }
 
-// One block: tile_tot becomes its exclusive scan, scan_chunk tiles a carry step: a thread at or
-// beyond the chunk adds 0 and stores nothing.
+// One block: tile_tot becomes its exclusive scan, scan_chunk tiles a carry step
+// (stage_common.h's block_scan_in_place).
 __global__ __launch_bounds__(AK_SCAN_BLOCK) void ack_rec_scan_kernel(AkRecArgs a) {
   __shared__ uint32_t wsum[AK_SCAN_BLOCK / 64];
   if (threadIdx.x < AK_S_WORDS) a.ctr[threadIdx.x] = 0;
   uint64_t m, total;
   if (!ak_rec_counts(a, &m, &total)) return;
-  const uint64_t tiles = ak_tiles_eff(total);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t chunk = a.scan_chunk && a.scan_chunk < AK_SCAN_BLOCK ? a.scan_chunk : AK_SCAN_BLOCK;
-  uint32_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < tiles;
-    const uint32_t x = mine ? a.tile_tot[t] : 0u;
-    uint32_t incl = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < AK_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) a.tile_tot[t] = carry + before + incl - x;
-    carry += all;
-    __syncthreads();
-  }
+  (void)block_scan_in_place<AK_SCAN_BLOCK>(a.tile_tot, a.tile_tot, ak_tiles_eff(total), wsum,
+                                           scan_chunk_of<AK_SCAN_BLOCK>(a.scan_chunk));
 }
 
 // a.w / 2 lanes a row.  The loop is uniform over the block: the shuffles see every lane.
@@ -256,7 +191,7 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_rec_rows_kernel(AkRecArgs a) {
       if (!ok) flags |= AK_F_BAD_SUB;
     }
   }
-  ak_report<4>(a.ctr, AK_R_SENDS, acc, flags);
+  block_report<4>(a.ctr, AK_R_SENDS, acc, flags, AK_S_FLAGS);
 }
 
 __global__ __launch_bounds__(AK_BLOCK) void ack_rec_place_kernel(AkRecArgs a) {
@@ -270,7 +205,7 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_rec_place_kernel(AkRecArgs a) {
     const uint64_t p0 = ts + static_cast<uint64_t>(threadIdx.x) * AK_ROWS;
     const uint32_t bits = ak_load_sends(a.verdicts, p0, total);
     uint32_t all;
-    uint32_t run = a.tile_tot[tile] + ak_block_scan(static_cast<uint32_t>(__popc(bits)), wsum, &all);
+    uint32_t run = a.tile_tot[tile] + block_excl_scan<AK_BLOCK>(static_cast<uint32_t>(__popc(bits)), wsum, &all);
     ak_tile_extent(a.inbox_offsets, m, ts, total, ext);
     uint64_t k = AK_NONE;
 #pragma unroll
@@ -493,7 +428,7 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_run_verdict_kernel(AkRunArgs a) 
         if (p0 + j < total) a.out_refs[p0 + j] = ref[j];
     }
   }
-  ak_report<5>(a.ctr, AK_A_OKS, acc, 0);
+  block_report<5>(a.ctr, AK_A_OKS, acc, 0, AK_S_FLAGS);
 }
 
 // a.w / 2 lanes a session.  The loop is uniform over the block: the shuffles see every lane.
@@ -554,7 +489,7 @@ __global__ __launch_bounds__(AK_BLOCK) void ack_run_rows_kernel(AkRunArgs a) {
       if (sub >= a.sub_limit) flags |= AK_F_BAD_SUB;
     }
   }
-  ak_report<1>(a.ctr, AK_A_RELEASED, acc, flags);
+  block_report<1>(a.ctr, AK_A_RELEASED, acc, flags, AK_S_FLAGS);
 }
 
 __global__ void ack_run_finish_kernel(AkRunArgs a) {

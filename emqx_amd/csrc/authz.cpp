@@ -25,6 +25,7 @@
 
 #include "../../include/emqx_authz.h"
 #include "authz.h"
+#include "stage_common.h"
 #ifndef EMQX_AUTHZ_NO_DEVICE
 #include "streams.h"
 #endif
@@ -841,19 +842,6 @@ int az_stats_get(emqx_authz* a, emqx_authz_stats* out) {
   return EMQX_OK;
 }
 
-}  // namespace
-
-namespace {
-template <class F>
-int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return EMQX_ENOMEM;
-  } catch (...) {
-    return EMQX_EINVAL;
-  }
-}
 }  // namespace
 
 extern "C" {

@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "stage_common.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define DV_HD __host__ __device__
@@ -104,18 +106,6 @@ DV_HD inline uint32_t dv_enrich(const DvView& v, uint32_t sub, uint32_t filter_w
   if (retain_in && ((s.opts & DV_SUB_RAP) || (flags & DV_MSG_RETAINED))) out |= DV_OUT_RETAIN;
   if (s.opts & DV_SUB_SUBID) *subid = s.subid;  // :595-598
   return out;
-}
-
-// The message of delivery d: the largest i in [0, n) with offsets[i] <= d (n >= 1).  At most 64
-// halvings whatever the offsets hold, and every index read lies in [0, n).
-DV_HD inline uint64_t dv_find_msg(const uint64_t* offsets, uint64_t n, uint64_t d) {
-  uint64_t lo = 0, hi = n;  // the answer lies in [lo, hi)
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] <= d) lo = mid;
-    else hi = mid;
-  }
-  return lo;
 }
 
 #if defined(__HIPCC__)

@@ -3,7 +3,7 @@
 // Work is distributed BY DELIVERY: a lane per delivery, a tile of DV_TILE consecutive deliveries
 // per block step, so a 10 K-subscriber message between empty ones spreads over 40 blocks instead
 // of serialising on one wave.  A lane finds its message by a bounded binary search over the
-// offsets (dv_find_msg); the lanes of a wave mostly walk the same path, so the loads coalesce
+// offsets (csr_find); the lanes of a wave mostly walk the same path, so the loads coalesce
 // into broadcasts.  The delivery count is read on the device as offsets[n]: the host sizes the
 // grid by cap_in only and the blocks stride over the tiles that exist.
 //
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(DV_TILE) void deliver_eval_kernel(DvArgs a) {
     const bool valid = d < total;
     uint32_t o = 0;
     if (valid) {
-      const uint64_t i = dv_find_msg(a.offsets, a.n, d);
+      const uint64_t i = csr_find(a.offsets, a.n, d);
       uint32_t subid;
       o = dv_enrich(a.v, a.subs[d], a.filters[d], a.msg_qos[i], a.msg_flags[i],
                     a.msg_from ? a.msg_from[i] : DV_NO_SENDER, &subid);
@@ -82,35 +82,13 @@ __global__ __launch_bounds__(DV_TILE) void deliver_eval_kernel(DvArgs a) {
 }
 
 // One block: tile_base = exclusive scan of tile_kept over the tiles of this call, scan_chunk
-// tiles a carry step: a thread at or beyond the chunk adds 0 and stores nothing.
+// tiles a carry step (stage_common.h's block_scan_in_place).
 __global__ __launch_bounds__(DV_SCAN_BLOCK) void deliver_scan_kernel(DvArgs a) {
   __shared__ uint64_t wsum[DV_SCAN_BLOCK / 64];
   const uint64_t total = dv_total(a);
   if (total == ~0ull) return;
-  const uint64_t n_tiles = (total + DV_TILE - 1) / DV_TILE;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t chunk = a.scan_chunk && a.scan_chunk < DV_SCAN_BLOCK ? a.scan_chunk : DV_SCAN_BLOCK;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < n_tiles; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < n_tiles;
-    const uint64_t x = mine ? a.tile_kept[t] : 0;
-    uint64_t incl = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(incl, d);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < DV_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) a.tile_base[t] = carry + before + incl - x;
-    carry += all;
-    __syncthreads();
-  }
+  (void)block_scan_in_place<DV_SCAN_BLOCK>(a.tile_kept, a.tile_base, (total + DV_TILE - 1) / DV_TILE, wsum,
+                                           scan_chunk_of<DV_SCAN_BLOCK>(a.scan_chunk));
 }
 
 __global__ __launch_bounds__(DV_TILE) void deliver_scatter_kernel(DvArgs a) {
@@ -134,7 +112,7 @@ __global__ __launch_bounds__(DV_TILE) void deliver_scatter_kernel(DvArgs a) {
     // deliveries kept before d: the tile's base, the tile's earlier waves, the wave's earlier lanes
     const uint64_t pos = a.tile_base[tile] + before + static_cast<uint32_t>(__popcll(b & ((1ull << lane) - 1ull)));
     if (valid) {
-      const uint64_t i = dv_find_msg(a.offsets, a.n, d);
+      const uint64_t i = csr_find(a.offsets, a.n, d);
       if (a.offsets[i] == d) a.kept_offsets[i] = pos;  // the first delivery of a non-empty message
       if (kept && write && pos < a.cap_kept) {
         a.kept_subs[pos] = a.subs[d];
@@ -173,7 +151,7 @@ __global__ __launch_bounds__(DV_TILE) void deliver_finish_kernel(DvArgs a) {
   if (d >= total) {
     a.kept_offsets[j] = n_kept;  // no delivery follows
   } else if (a.offsets[j + 1] <= d) {
-    const uint64_t i = dv_find_msg(a.offsets, a.n, d);  // the last message that starts at d: the non-empty one
+    const uint64_t i = csr_find(a.offsets, a.n, d);  // the last message that starts at d: the non-empty one
     if (i != j) a.kept_offsets[j] = a.kept_offsets[i];
   }
 }

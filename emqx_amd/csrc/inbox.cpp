@@ -1,8 +1,8 @@
 // C ABI of the inbox stage (include/emqx_inbox.h): the handle and its device scratch, the three
-// device entry points and the host evaluator.  The digit and pass arithmetic and the message
-// lookup live in inbox.h and are the same code on both sides.  With EMQX_INBOX_NO_DEVICE this
-// file compiles with a plain C++ compiler into the host-only part (tests/c/test_inbox_host.cpp):
-// handles of device EMQX_INBOX_HOST_ONLY alone.
+// device entry points and the host evaluator.  The digit and pass arithmetic lives in inbox.h and
+// is the same code on both sides.  With EMQX_INBOX_NO_DEVICE this file compiles with a plain C++
+// compiler into the host-only part (tests/c/test_inbox_host.cpp): handles of device
+// EMQX_INBOX_HOST_ONLY alone.
 #ifndef EMQX_INBOX_NO_DEVICE
 #include <hip/hip_runtime.h>
 #endif
@@ -520,18 +520,6 @@ int inbox_stats_get(emqx_inbox* h, emqx_inbox_stats* out) {
   s.size = nbytes;
   std::memcpy(out, &s, nbytes);
   return EMQX_OK;
-}
-
-// No exception (std::bad_alloc of the containers) crosses the C ABI.
-template <class F>
-int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return EMQX_ENOMEM;
-  } catch (...) {
-    return EMQX_EINVAL;
-  }
 }
 
 }  // namespace

@@ -1,9 +1,11 @@
 // Shared pieces of the inbox stage (include/emqx_inbox.h): the digit and pass
-// arithmetic from sub_limit, the message lookup and the constants.  Everything here is
-// __host__ __device__: the kernels (inbox_kernels.hip) and the host side (inbox.cpp) run the
-// same functions.
+// arithmetic from sub_limit and the constants; the message lookup is stage_common.h's csr_find.
+// Everything here is __host__ __device__: the kernels (inbox_kernels.hip) and the host side
+// (inbox.cpp) run the same functions.
 #pragma once
 #include <stdint.h>
+
+#include "stage_common.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -49,18 +51,6 @@ IB_HD inline uint32_t ib_passes(uint64_t sub_limit) {
 IB_HD inline uint32_t ib_digit(uint32_t key, uint32_t pass) { return (key >> (pass * IB_DIGIT_BITS)) & (IB_RADIX - 1); }
 
 IB_HD inline uint64_t ib_tiles(uint64_t total) { return (total + IB_TILE - 1) / IB_TILE; }
-
-// The message of delivery d: the largest i in [0, n) with offsets[i] <= d (n >= 1); deliver.h's
-// dv_find_msg.  At most 64 halvings whatever the offsets hold, every index read lies in [0, n).
-IB_HD inline uint64_t ib_find_msg(const uint64_t* offsets, uint64_t n, uint64_t d) {
-  uint64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] <= d) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 #if defined(__HIPCC__)
 // Arguments of the device passes; the first block of pointers is emqx_inbox_batch's.

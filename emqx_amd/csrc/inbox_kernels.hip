@@ -76,14 +76,14 @@ __device__ inline uint64_t ib_peers(uint32_t digit, bool valid) {
 // What the first kernel over the input does for delivery d besides its key: the message index,
 // the count of first deliveries (one a non-empty message), the subscriber bound.
 __device__ inline void ib_first_look(const IbArgs& a, uint64_t d, uint32_t sub, uint32_t* msgs, bool* bad) {
-  const uint64_t i = ib_find_msg(a.offsets, a.n, d);
+  const uint64_t i = csr_find(a.offsets, a.n, d);
   a.msg_of[d] = static_cast<uint32_t>(i);
   if (a.offsets[i] == d) ++*msgs;
   if (sub >= a.sub_limit) *bad = true;
 }
 
 __device__ inline void ib_first_report(const IbArgs& a, uint32_t msgs, bool bad) {
-  for (uint32_t d = 32; d >= 1; d >>= 1) msgs += __shfl_xor(msgs, d, 64);
+  msgs = wave_sum(msgs);
   const bool any_bad = __any(bad);
   if ((threadIdx.x & 63u) == 0) {
     if (msgs) atomicAdd(a.ctr + IB_S_MSGS, static_cast<unsigned long long>(msgs));
@@ -128,49 +128,23 @@ __global__ __launch_bounds__(IB_BLOCK) void inbox_hist_kernel(IbArgs a, uint32_t
   if (FIRST) ib_first_report(a, msgs, bad);
 }
 
-// Tile totals a one-block scan takes per carry step: a thread at or beyond it adds 0 and stores
-// nothing, but takes part in the shuffles and barriers.
-__device__ inline uint32_t ib_chunk(const IbArgs& a) {
-  return a.scan_chunk && a.scan_chunk < IB_SCAN_BLOCK ? a.scan_chunk : IB_SCAN_BLOCK;
-}
-
 // Block `digit`: tile_hist[digit][*] becomes the position of the digit's first delivery of each
-// tile: the deliveries of the lower digits, then the digit's deliveries of the earlier tiles.
+// tile: the deliveries of the lower digits, then the digit's deliveries of the earlier tiles
+// (stage_common.h's block_scan_in_place from that start, scan_chunk tiles a carry step).
 __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_scan_kernel(IbArgs a, uint32_t pass) {
   __shared__ uint32_t wsum[IB_SCAN_BLOCK / 64];
   const uint64_t total = ib_go(a, false);
   if (total == ~0ull) return;
   const uint64_t tiles = ib_tiles(total);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, digit = blockIdx.x;
-  uint32_t v = threadIdx.x < digit ? a.digit_tot[pass * IB_RADIX + threadIdx.x] : 0u;
-  for (uint32_t d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if (lane == 0) wsum[wave] = v;
+  const uint32_t digit = blockIdx.x;
+  const uint32_t v = wave_sum(threadIdx.x < digit ? a.digit_tot[pass * IB_RADIX + threadIdx.x] : 0u);
+  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
-  uint32_t carry = 0;
-  for (uint32_t w = 0; w < IB_SCAN_BLOCK / 64; ++w) carry += wsum[w];
-  __syncthreads();
+  uint32_t below = 0;
+  for (uint32_t w = 0; w < IB_SCAN_BLOCK / 64; ++w) below += wsum[w];
+  // (the scan's first barrier: every thread has read wsum)
   uint32_t* hist = a.tile_hist + static_cast<uint64_t>(digit) * tiles;
-  const uint32_t chunk = ib_chunk(a);
-  for (uint64_t base = 0; base < tiles; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < tiles;
-    const uint32_t x = mine ? hist[t] : 0u;
-    uint32_t incl = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < IB_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) hist[t] = carry + before + incl - x;
-    carry += all;
-    __syncthreads();
-  }
+  (void)block_scan_in_place<IB_SCAN_BLOCK>(hist, hist, tiles, wsum, scan_chunk_of<IB_SCAN_BLOCK>(a.scan_chunk), below);
 }
 
 // The payloads of the delivery at input position `src` written at inbox position `pos`.
@@ -313,8 +287,8 @@ __global__ __launch_bounds__(IB_BLOCK) void inbox_heads_kernel(IbArgs a, const u
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     uint32_t mine[IB_ROWS];
-    uint32_t c = __popc(ib_head_bits(keys, total, tile * IB_TILE + static_cast<uint64_t>(threadIdx.x) * IB_ROWS, mine));
-    for (uint32_t d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    const uint32_t bits = ib_head_bits(keys, total, tile * IB_TILE + static_cast<uint64_t>(threadIdx.x) * IB_ROWS, mine);
+    const uint32_t c = wave_sum<uint32_t>(__popc(bits));
     if (lane == 0) wsum[wave] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -331,31 +305,9 @@ __global__ __launch_bounds__(IB_SCAN_BLOCK) void inbox_hscan_kernel(IbArgs a) {
   __shared__ uint32_t wsum[IB_SCAN_BLOCK / 64];
   const uint64_t total = ib_go(a, false);
   if (total == ~0ull) return;
-  const uint64_t tiles = ib_tiles(total);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t chunk = ib_chunk(a);
-  uint32_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < tiles;
-    const uint32_t x = mine ? a.tile_heads[t] : 0u;
-    uint32_t incl = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < IB_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) a.tile_hbase[t] = carry + before + incl - x;
-    carry += all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.ctr[IB_S_BOXES] = carry;
+  const uint32_t m = block_scan_in_place<IB_SCAN_BLOCK>(a.tile_heads, a.tile_hbase, ib_tiles(total), wsum,
+                                                        scan_chunk_of<IB_SCAN_BLOCK>(a.scan_chunk));
+  if (threadIdx.x == 0) a.ctr[IB_S_BOXES] = m;
 }
 
 __global__ __launch_bounds__(IB_BLOCK) void inbox_starts_kernel(IbArgs a, const uint32_t* keys, uint32_t* starts) {
@@ -363,22 +315,13 @@ __global__ __launch_bounds__(IB_BLOCK) void inbox_starts_kernel(IbArgs a, const 
   const uint64_t total = ib_go(a, false);
   if (total == ~0ull) return;
   const uint64_t tiles = ib_tiles(total);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const uint64_t k0 = tile * IB_TILE + static_cast<uint64_t>(threadIdx.x) * IB_ROWS;
     uint32_t mine[IB_ROWS];
     const uint32_t bits = ib_head_bits(keys, total, k0, mine);
-    const uint32_t c = __popc(bits);
-    uint32_t incl = c;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t r = a.tile_hbase[tile] + incl - c;  // heads before this thread's first position
-    for (uint32_t w = 0; w < IB_WAVES; ++w)
-      if (w < wave) r += wsum[w];
+    uint32_t tile_heads;  // (not used: the scan kernel has the tile's base)
+    // heads before this thread's first position
+    uint64_t r = a.tile_hbase[tile] + block_excl_scan<IB_BLOCK, uint32_t>(__popc(bits), wsum, &tile_heads);
 #pragma unroll
     for (uint32_t j = 0; j < IB_ROWS; ++j) {
       if (!(bits & (1u << j))) continue;
@@ -388,7 +331,6 @@ __global__ __launch_bounds__(IB_BLOCK) void inbox_starts_kernel(IbArgs a, const 
       if (r <= a.cap_boxes) a.inbox_offsets[r] = k;
       ++r;
     }
-    __syncthreads();
   }
 }
 

@@ -44,46 +44,6 @@ __device__ inline bool rt_count(const uint64_t* n_boxes, uint64_t m_arg, uint64_
   return *m <= cap_boxes && *m <= AK_MAX_TOTAL && (subs || *m <= sub_limit);
 }
 
-// The block's sums of N per-thread values into ctr[word0 ..], and flag bits into ctr[RT_S_FLAGS].
-// Every thread of the block calls it.
-template <uint32_t N>
-__device__ inline void rt_report(unsigned long long* ctr, uint32_t word0, const uint64_t (&v)[N], uint32_t flags) {
-  __shared__ unsigned long long red[N];
-  __shared__ uint32_t red_flags;
-  if (threadIdx.x < N) red[threadIdx.x] = 0;
-  if (threadIdx.x == 0) red_flags = 0;
-  __syncthreads();
-#pragma unroll
-  for (uint32_t c = 0; c < N; ++c) {
-    uint64_t s = v[c];
-    for (uint32_t d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&red[c], static_cast<unsigned long long>(s));
-  }
-  if (flags) atomicOr(&red_flags, flags);
-  __syncthreads();
-  if (threadIdx.x < N && red[threadIdx.x]) atomicAdd(ctr + word0 + threadIdx.x, red[threadIdx.x]);
-  if (threadIdx.x == N && red_flags) atomicOr(ctr + RT_S_FLAGS, static_cast<unsigned long long>(red_flags));
-}
-
-// Exclusive scan of x over the block.  Two barriers.
-__device__ inline uint32_t rt_block_scan(uint32_t x, uint32_t* wsum) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t incl = x;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  __syncthreads();  // the readers of the scan before this one are done
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < RT_WAVES; ++w)
-    if (w < wave) before += wsum[w];
-  return before + incl - x;
-}
-
 // ---- stamp -------------------------------------------------------------------------------------
 
 __global__ void retry_init_kernel(unsigned long long* ctr) {
@@ -114,7 +74,7 @@ __global__ __launch_bounds__(AK_BLOCK) void retry_stamp_kernel(RtStampArgs a) {
     if (n0 != t.x || n1 != t.y) *at = make_ulonglong2(n0, n1);
     if (j == 0) acc[0] += 1;
   }
-  rt_report<4>(a.ctr, RT_S_ROWS, acc, flags);
+  block_report<4>(a.ctr, RT_S_ROWS, acc, flags, RT_S_FLAGS);
 }
 
 __global__ void retry_stamp_finish_kernel(RtStampArgs a) {
@@ -175,7 +135,7 @@ __global__ __launch_bounds__(AK_BLOCK) void retry_count_kernel(RtSweepArgs a) {
         c = (rt_is_item(a.mode, s.x, t.x, a.now_ms, interval) ? 1u : 0u) + (rt_is_item(a.mode, s.z, t.y, a.now_ms, interval) ? 1u : 0u);
       }
     }
-    for (uint32_t d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    c = wave_sum(c);
     __syncthreads();  // the readers of the trip before are done
     if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -187,42 +147,20 @@ __global__ __launch_bounds__(AK_BLOCK) void retry_count_kernel(RtSweepArgs a) {
   }
 }
 
-// One block: tile_tot becomes its exclusive scan, scan_chunk tiles a carry step: a thread at or
-// beyond the chunk adds 0 and stores nothing.
+// One block: tile_tot becomes its exclusive scan, scan_chunk tiles a carry step
+// (stage_common.h's block_scan_in_place).
 __global__ __launch_bounds__(AK_SCAN_BLOCK) void retry_scan_kernel(RtSweepArgs a) {
   __shared__ uint64_t wsum[AK_SCAN_BLOCK / 64];
   if (threadIdx.x < RT_C_WORDS) a.ctr[threadIdx.x] = 0;
   uint64_t m;
   if (!rt_sweep_count(a, &m)) return;
-  const uint64_t tiles = rt_tiles(m, a.w);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t chunk = a.scan_chunk && a.scan_chunk < AK_SCAN_BLOCK ? a.scan_chunk : AK_SCAN_BLOCK;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < tiles;
-    const uint64_t x = mine ? a.tile_tot[t] : 0ull;
-    uint64_t incl = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < AK_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) a.tile_tot[t] = carry + before + incl - x;
-    carry += all;
-    __syncthreads();
-  }
+  const uint64_t total = block_scan_in_place<AK_SCAN_BLOCK>(a.tile_tot, a.tile_tot, rt_tiles(m, a.w), wsum,
+                                                            scan_chunk_of<AK_SCAN_BLOCK>(a.scan_chunk));
   __syncthreads();  // the zeroing above
   if (threadIdx.x == 0) {
-    a.ctr[RT_C_TOTAL] = carry;
-    a.ctr[RT_C_FULL] = carry > a.cap_out ? 1ull : 0ull;
-    a.out_offsets[m] = carry;
+    a.ctr[RT_C_TOTAL] = total;
+    a.ctr[RT_C_FULL] = total > a.cap_out ? 1ull : 0ull;
+    a.out_offsets[m] = total;
   }
 }
 
@@ -269,7 +207,8 @@ __global__ __launch_bounds__(AK_BLOCK) void retry_emit_kernel(RtSweepArgs a) {
       young_age = y > young_age ? y : young_age;
     }
     const uint32_t items = packed & 0xFFu;
-    const uint32_t pre = rt_block_scan(j == 0 ? items : 0u, wsum);
+    uint32_t tile_items;  // (not used: the scan kernel has the tile's base)
+    const uint32_t pre = block_excl_scan<AK_BLOCK>(j == 0 ? items : 0u, wsum, &tile_items);
     const uint64_t off = a.tile_tot[base / per_block] + __shfl(pre, head, 64);
     // the rank of an item among its row's items: the keys below its own, ties by slot index
     uint32_t rank[2] = {0, 0};
@@ -326,7 +265,7 @@ __global__ __launch_bounds__(AK_BLOCK) void retry_emit_kernel(RtSweepArgs a) {
       if (sub >= a.sub_limit) flags |= RT_F_BAD_SUB;
     }
   }
-  rt_report<7>(a.ctr, RT_S_ROWS, acc, flags);
+  block_report<7>(a.ctr, RT_S_ROWS, acc, flags, RT_S_FLAGS);
 }
 
 __global__ void retry_sweep_finish_kernel(RtSweepArgs a) {

@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "stage_common.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define RT_HD __host__ __device__
@@ -52,18 +54,6 @@ RT_HD inline uint64_t rt_fwd_mask(const RtRec& r, uint32_t local) { return r.nod
 RT_HD inline RtRec rt_record(const RtRec* recs, uint64_t n_slots, uint32_t f) {
   if (f < n_slots) return recs[f];
   return RtRec{0, 0, 0};
-}
-
-// The message of entry d: the largest i in [0, n) with offsets[i] <= d (n >= 1).  At most 64
-// halvings whatever the offsets hold, and every index read lies in [0, n).
-RT_HD inline uint64_t rt_find_msg(const uint64_t* offsets, uint64_t n, uint64_t d) {
-  uint64_t lo = 0, hi = n;  // the answer lies in [lo, hi)
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] <= d) lo = mid;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // Tuning key "scan_chunk": the elements the one-block scans take per carry step, at most this.

@@ -59,23 +59,6 @@ __device__ inline uint64_t rt_total(const RtArgs& a) {
   return t <= a.cap_in ? t : ~0ull;
 }
 
-template <class T>
-__device__ inline T wave_incl_scan(T x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-__device__ inline uint64_t wave_sum(uint64_t x) {
-#pragma unroll
-  for (uint32_t d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
 // Exclusive prefix, in entry order over the tile, of the per-entry values x[row]; *all: the
 // tile's sum.  `chunk` is [RT_CHUNKS] of LDS, free again after the call.  Two barriers.
 template <class T>
@@ -95,18 +78,6 @@ __device__ inline void tile_scan(const T x[RT_ROWS], T pre[RT_ROWS], T* all, T* 
   for (uint32_t r = 0; r < RT_ROWS; ++r) pre[r] += __shfl(ce, static_cast<int>(r * RT_WAVES + wave), 64);
   *all = __shfl(ci, static_cast<int>(RT_CHUNKS - 1), 64);
   __syncthreads();
-}
-
-// The first k in [0, m) with offsets[k] >= x, else m.  At most 64 halvings whatever the offsets
-// hold; every index read lies in [0, m).
-__device__ inline uint64_t rt_lower(const uint64_t* offsets, uint64_t m, uint64_t x) {
-  uint64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // The entries of one tile as a thread holds them: row r is entry ts + r * RT_BLOCK + threadIdx.x.
@@ -224,8 +195,8 @@ __global__ __launch_bounds__(RT_BLOCK) void route_count_kernel(RtArgs a) {
     __syncthreads();
     // the messages whose head lies in [ts, ts + RT_TILE); the last tile also takes the heads at
     // its end (messages without entries behind the last entry, and offsets[n] itself)
-    const uint64_t k_lo = rt_lower(a.offsets, a.n + 1, ts);
-    const uint64_t k_hi = last ? a.n + 1 : rt_lower(a.offsets, a.n + 1, ts + RT_TILE);
+    const uint64_t k_lo = csr_lower(a.offsets, 0, a.n + 1, ts);
+    const uint64_t k_hi = last ? a.n + 1 : csr_lower(a.offsets, 0, a.n + 1, ts + RT_TILE);
     for (uint64_t k = k_lo + threadIdx.x; k < k_hi; k += RT_BLOCK) {
       const uint64_t off = a.offsets[k];
       const uint64_t p = off < total ? off : total;
@@ -240,41 +211,18 @@ __global__ __launch_bounds__(RT_BLOCK) void route_count_kernel(RtArgs a) {
   if (lane == 0 && unknown) atomicAdd(a.ctr + RT_S_UNKNOWN, static_cast<unsigned long long>(unknown));
 }
 
-// One block: x[0, m) becomes its exclusive scan, `chunk` elements a carry step (a thread at or
-// beyond the chunk adds 0 and stores nothing); returns the sum in every thread.
-__device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum, uint32_t chunk) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < m; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < m;
-    const uint64_t v = mine ? x[t] : 0;
-    const uint64_t incl = wave_incl_scan(v);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < RT_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) x[t] = carry + before + incl - v;
-    carry += all;
-    __syncthreads();
-  }
-  return carry;
-}
-
 __global__ __launch_bounds__(RT_SCAN_BLOCK) void route_scan_kernel(RtArgs a) {
   __shared__ uint64_t wsum[RT_SCAN_BLOCK / 64];
   const uint64_t total = rt_total(a);
   if (total == ~0ull) return;
   const uint64_t tiles = rt_tiles(total);
-  const uint32_t chunk = a.scan_chunk && a.scan_chunk < RT_SCAN_BLOCK ? a.scan_chunk : RT_SCAN_BLOCK;
-  const uint64_t fwd = scan_in_place(a.tile_hist, RT_NODES * tiles, wsum, chunk);
-  (void)scan_in_place(a.tile_routes, tiles, wsum, chunk);
-  const uint64_t kept = scan_in_place(a.tile_kept, tiles, wsum, chunk);
-  (void)scan_in_place(a.tile_hasfwd, tiles, wsum, chunk);
-  (void)scan_in_place(a.tile_fwd, tiles, wsum, chunk);
+  const uint32_t chunk = scan_chunk_of<RT_SCAN_BLOCK>(a.scan_chunk);
+  const uint64_t fwd = block_scan_in_place<RT_SCAN_BLOCK>(a.tile_hist, a.tile_hist, RT_NODES * tiles, wsum, chunk);
+  (void)block_scan_in_place<RT_SCAN_BLOCK>(a.tile_routes, a.tile_routes, tiles, wsum, chunk);
+  const uint64_t kept = block_scan_in_place<RT_SCAN_BLOCK>(a.tile_kept, a.tile_kept, tiles, wsum, chunk);
+  (void)block_scan_in_place<RT_SCAN_BLOCK>(a.tile_hasfwd, a.tile_hasfwd, tiles, wsum, chunk);
+  (void)block_scan_in_place<RT_SCAN_BLOCK>(a.tile_fwd, a.tile_fwd, tiles, wsum, chunk);
+  // (tiles >= 1: the barriers of the later scans stand between the stores of the first and these loads)
   if (threadIdx.x < RT_NODES) a.node_offsets[threadIdx.x] = a.tile_hist[static_cast<uint64_t>(threadIdx.x) * tiles];
   if (threadIdx.x == 0) {
     a.node_offsets[RT_NODES] = fwd;
@@ -377,7 +325,7 @@ __global__ __launch_bounds__(RT_BLOCK) void route_scatter_kernel(RtArgs a) {
         const uint64_t m = t.m[r];
         const uint32_t c = r * RT_WAVES + wave;
         // n >= 1 here: an entry exists
-        const uint32_t msg = m ? static_cast<uint32_t>(rt_find_msg(a.offsets, a.n, ts + r * RT_BLOCK + threadIdx.x)) : 0u;
+        const uint32_t msg = m ? static_cast<uint32_t>(csr_find(a.offsets, a.n, ts + r * RT_BLOCK + threadIdx.x)) : 0u;
         for (uint64_t u = a.fwd_nodes; u; u &= u - 1) {
           const uint32_t v = static_cast<uint32_t>(__builtin_ctzll(u));
           const uint64_t b = __ballot((m >> v) & 1ull);
@@ -415,7 +363,7 @@ __global__ __launch_bounds__(RT_BLOCK) void route_expand_kernel(RtArgs a) {
       for (uint32_t r = 0; r < RT_ROWS; ++r) {
         uint64_t m = t.m[r];
         if (!m) continue;
-        const uint64_t msg = rt_find_msg(a.offsets, a.n, ts + r * RT_BLOCK + threadIdx.x);
+        const uint64_t msg = csr_find(a.offsets, a.n, ts + r * RT_BLOCK + threadIdx.x);
         uint64_t pos = base + pf[r];
         for (; m; m &= m - 1, ++pos)  // the yardstick expands per dest
           if (pos < a.cap_fwd) {

@@ -601,18 +601,6 @@ int own_stats_get(emqx_owntab* h, emqx_owntab_stats* out) {
   return EMQX_OK;
 }
 
-// No exception (std::bad_alloc of the containers) crosses the C ABI.
-template <class F>
-int guarded(F f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return EMQX_ENOMEM;
-  } catch (...) {
-    return EMQX_EINVAL;
-  }
-}
-
 }  // namespace
 
 extern "C" {

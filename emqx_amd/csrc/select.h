@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "stage_common.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define SL_HD __host__ __device__
@@ -129,18 +131,6 @@ SL_HD inline SlCount sl_entry(const SlView& v, const uint32_t* filters, uint64_t
     ++c.kept;
   }
   return c;
-}
-
-// The message of entry d: the largest i in [0, n) with offsets[i] <= d (n >= 1).  At most 64
-// halvings whatever the offsets hold, and every index read lies in [0, n).
-SL_HD inline uint64_t sl_find_msg(const uint64_t* offsets, uint64_t n, uint64_t d) {
-  uint64_t lo = 0, hi = n;  // the answer lies in [lo, hi)
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] <= d) lo = mid;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // Tuning key "scan_chunk": the elements the one-block scans take per carry step, at most this.

@@ -3,14 +3,14 @@
 // Work is distributed BY CSR ENTRY, as deliver_kernels.hip distributes by delivery: a lane per
 // entry, a tile of SL_TILE consecutive entries per block step, so a message that matched 5 000
 // filters between empty ones spreads over 20 blocks.  A lane finds its message by a bounded
-// binary search over the offsets (sl_find_msg) and evaluates sl_entry (select.h, the code the
+// binary search over the offsets (csr_find) and evaluates sl_entry (select.h, the code the
 // host evaluator runs): the owners its entry adds to the message's set, deduplicated by looking
 // back over the earlier entries of the same message, across wave and tile boundaries, back to
 // offsets[i].  The entry count is read on the device as offsets[n]: the host sizes the grid by
 // cap_in only and the blocks stride over the tiles that exist.
 //
-// An entry adds any number of owners, so the ranks are prefix sums of counts (a wave scan by
-// __shfl_up, the waves of a block through LDS), not ballots.  The passes, each a kernel
+// An entry adds any number of owners, so the ranks are prefix sums of counts (stage_common.h's
+// block_excl_scan), not ballots.  The passes, each a kernel
 // boundary on the stream (no inter-block waiting):
 //   1  select_count_kernel    by entry: entry_kept[d], the tile's sum, the summary counters (one
 //                             atomic a counter a block);
@@ -51,33 +51,6 @@ __device__ inline uint64_t sl_total(const SlArgs& a) {
 
 __device__ inline uint32_t sl_mask(const SlArgs& a, uint64_t i) { return a.msg_classes ? a.msg_classes[i] : 0xFFFFFFFFu; }
 
-// Sum of x over the wave, in every lane.
-__device__ inline uint64_t wave_sum(uint64_t x) {
-  for (uint32_t d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  return x;
-}
-
-// Exclusive prefix of x over the SL_TILE threads of the block and the block's sum; `ws` is
-// [SL_WAVES] of LDS, free again after the call.
-__device__ inline uint64_t tile_excl_scan(uint64_t x, uint64_t* ws, uint64_t* sum) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t incl = x;
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(incl, d);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) ws[wave] = incl;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-  for (uint32_t w = 0; w < SL_WAVES; ++w) {
-    if (w < wave) before += ws[w];
-    all += ws[w];
-  }
-  __syncthreads();
-  *sum = all;
-  return before + incl - x;
-}
-
 __global__ __launch_bounds__(SL_TILE) void select_count_kernel(SlArgs a) {
   __shared__ uint64_t part[4][SL_WAVES];
   const uint64_t total = sl_total(a);
@@ -88,13 +61,14 @@ __global__ __launch_bounds__(SL_TILE) void select_count_kernel(SlArgs a) {
     const uint64_t d = tile * SL_TILE + threadIdx.x;
     SlCount c{0, 0, 0, 0};
     if (d < total) {
-      const uint64_t i = sl_find_msg(a.offsets, a.n, d);
+      const uint64_t i = csr_find(a.offsets, a.n, d);
       uint64_t s = a.offsets[i];
       if (s > d) s = d;  // offsets that are no CSR: the look-back stays below d
       c = sl_entry(a.v, a.filters, s, d, sl_mask(a, i), nullptr, 0);
       a.entry_kept[d] = c.kept;
     }
-    const uint64_t w[4] = {wave_sum(c.kept), wave_sum(c.examined), wave_sum(c.dups), wave_sum(c.unknown)};
+    const uint64_t w[4] = {wave_sum<uint64_t>(c.kept), wave_sum<uint64_t>(c.examined), wave_sum<uint64_t>(c.dups),
+                           wave_sum<uint64_t>(c.unknown)};
     if (lane == 0)
       for (uint32_t k = 0; k < 4; ++k) part[k][wave] = w[k];
     __syncthreads();
@@ -119,47 +93,21 @@ __global__ __launch_bounds__(SL_TILE) void select_macount_kernel(SlArgs a) {
     const uint64_t j = tile * SL_TILE + threadIdx.x;
     const uint64_t c = j < a.n ? sl_match_all_count(a.v, sl_mask(a, j)) : 0;
     uint64_t sum;
-    const uint64_t before = tile_excl_scan(c, ws, &sum);
+    const uint64_t before = block_excl_scan<SL_TILE>(c, ws, &sum);
     if (j < a.n) a.ma_before[j] = before;
     if (threadIdx.x == 0) a.mtile_base[tile] = sum;  // scanned in place by pass 3
   }
-}
-
-// One block: x[0, m) becomes its exclusive scan, `chunk` elements a carry step (a thread at or
-// beyond the chunk adds 0 and stores nothing); returns the sum in every thread.
-__device__ inline uint64_t scan_in_place(uint64_t* x, uint64_t m, uint64_t* wsum, uint32_t chunk) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < m; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < m;
-    const uint64_t v = mine ? x[t] : 0;
-    uint64_t incl = v;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(incl, d);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < SL_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) x[t] = carry + before + incl - v;
-    carry += all;
-    __syncthreads();
-  }
-  return carry;
 }
 
 __global__ __launch_bounds__(SL_SCAN_BLOCK) void select_scan_kernel(SlArgs a) {
   __shared__ uint64_t wsum[SL_SCAN_BLOCK / 64];
   const uint64_t total = sl_total(a);
   if (total == ~0ull) return;
-  const uint32_t chunk = a.scan_chunk && a.scan_chunk < SL_SCAN_BLOCK ? a.scan_chunk : SL_SCAN_BLOCK;
-  const uint64_t by_entry = scan_in_place(a.tile_base, (total + SL_TILE - 1) / SL_TILE, wsum, chunk);
-  const uint64_t by_all = scan_in_place(a.mtile_base, (a.n + SL_TILE - 1) / SL_TILE, wsum, chunk);
+  const uint32_t chunk = scan_chunk_of<SL_SCAN_BLOCK>(a.scan_chunk);
+  const uint64_t by_entry =
+      block_scan_in_place<SL_SCAN_BLOCK>(a.tile_base, a.tile_base, (total + SL_TILE - 1) / SL_TILE, wsum, chunk);
+  const uint64_t by_all =
+      block_scan_in_place<SL_SCAN_BLOCK>(a.mtile_base, a.mtile_base, (a.n + SL_TILE - 1) / SL_TILE, wsum, chunk);
   if (threadIdx.x == 0) {
     a.ctr[SL_C_ENTRY_TOTAL] = by_entry;
     a.ctr[SL_S_SELECTED] = by_entry + by_all;
@@ -176,9 +124,9 @@ __global__ __launch_bounds__(SL_TILE) void select_write_kernel(SlArgs a) {
     const bool valid = d < total;
     const uint32_t kept = valid ? a.entry_kept[d] : 0u;
     uint64_t sum;
-    const uint64_t before = tile_excl_scan(kept, ws, &sum);
-    if (!valid) continue;  // no barrier follows in this step
-    const uint64_t i = sl_find_msg(a.offsets, a.n, d);
+    const uint64_t before = block_excl_scan<SL_TILE, uint64_t>(kept, ws, &sum);
+    if (!valid) continue;  // no barrier follows in this step; every thread reaches the next step's scan
+    const uint64_t i = csr_find(a.offsets, a.n, d);
     const uint32_t mask = sl_mask(a, i);
     const uint64_t own = sl_match_all_count(a.v, mask);
     // the owners of every earlier message and of this one's match-all list, then of the earlier entries
@@ -216,7 +164,7 @@ __global__ __launch_bounds__(SL_TILE) void select_empty_kernel(SlArgs a) {
     const uint64_t ma = a.mtile_base[j / SL_TILE] + a.ma_before[j];
     uint64_t by_entry = a.ctr[SL_C_ENTRY_TOTAL];  // no entry follows
     if (d < total) {
-      const uint64_t i = sl_find_msg(a.offsets, a.n, d);  // the last message that starts at d: the one with entries
+      const uint64_t i = csr_find(a.offsets, a.n, d);  // the last message that starts at d: the one with entries
       by_entry = a.out_offsets[i] - (a.mtile_base[i / SL_TILE] + a.ma_before[i]);
     }
     const uint64_t at = ma + by_entry;

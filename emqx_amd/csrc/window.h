@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "stage_common.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define WN_HD __host__ __device__
@@ -148,18 +150,6 @@ WN_HD inline uint8_t wn_verdict(const WnPlan& p, uint8_t o, uint32_t a, uint32_t
 }
 
 WN_HD inline uint64_t wn_tiles(uint64_t total) { return (total + WN_TILE - 1) / WN_TILE; }
-
-// The first k in [0, n] with offsets[k] >= x (n when there is none).  At most 64 halvings
-// whatever the offsets hold, every index read lies in [0, n).
-WN_HD inline uint64_t wn_lower(const uint64_t* offsets, uint64_t n, uint64_t x) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (offsets[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 #if defined(__HIPCC__)
 // Arguments of the device passes; the first block is emqx_window_batch's.

@@ -69,29 +69,8 @@ __device__ inline void wn_load_opts(const uint8_t* opts, uint64_t p0, uint64_t t
   }
 }
 
-// Exclusive scan of x over the block (sums of three packed 16-bit fields never carry: a tile
-// holds 2048 deliveries); *all: the block's sum.  Two barriers.
-__device__ inline uint64_t wn_block_scan(uint64_t x, uint64_t* wsum, uint64_t* all) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t incl = x;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  __syncthreads();  // the readers of the scan before this one are done
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint64_t before = 0, sum = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < WN_WAVES; ++w) {
-    if (w < wave) before += wsum[w];
-    sum += wsum[w];
-  }
-  *all = sum;
-  return before + incl - x;
-}
-
+// What a delivery adds to the block scans: three packed 16-bit fields, whose sums never carry (a
+// tile holds 2048 deliveries).
 constexpr uint64_t WN_ONE_A = 1ull, WN_ONE_Z = 1ull << 16, WN_ONE_H = 1ull << 32;
 __device__ inline uint64_t wn_indicator(uint8_t o) {
   const uint32_t l = wn_live(o);
@@ -124,7 +103,7 @@ __global__ __launch_bounds__(WN_BLOCK) void window_heads_kernel(WnArgs a) {
 #pragma unroll
     for (uint32_t j = 0; j < WN_ROWS; ++j) x += wn_indicator(o[j]);
     uint64_t all;
-    uint64_t run = wn_block_scan(x, wsum, &all);
+    uint64_t run = block_excl_scan<WN_BLOCK>(x, wsum, &all);
 #pragma unroll
     for (uint32_t j = 0; j < WN_ROWS; ++j) {
       pre[threadIdx.x * WN_ROWS + j] = static_cast<uint32_t>(run);
@@ -137,8 +116,8 @@ __global__ __launch_bounds__(WN_BLOCK) void window_heads_kernel(WnArgs a) {
     __syncthreads();
     // the inboxes whose head lies in [ts, ts + WN_TILE); the last tile also takes the heads at
     // its end (inboxes without deliveries behind the last delivery, and inbox_offsets[m] itself)
-    const uint64_t k_lo = wn_lower(a.inbox_offsets, m + 1, ts);
-    const uint64_t k_hi = last ? m + 1 : wn_lower(a.inbox_offsets, m + 1, ts + WN_TILE);
+    const uint64_t k_lo = csr_lower(a.inbox_offsets, 0, m + 1, ts);
+    const uint64_t k_hi = last ? m + 1 : csr_lower(a.inbox_offsets, 0, m + 1, ts + WN_TILE);
     for (uint64_t k = k_lo + threadIdx.x; k < k_hi; k += WN_BLOCK) {
       const uint64_t off = a.inbox_offsets[k];
       const uint64_t p = off < total ? off : total;
@@ -149,36 +128,14 @@ __global__ __launch_bounds__(WN_BLOCK) void window_heads_kernel(WnArgs a) {
 }
 
 // One block: tile_tot becomes its exclusive scan (neither half reaches 2^32: no carry between them),
-// scan_chunk tiles a carry step: a thread at or beyond the chunk adds 0 and stores nothing.
+// scan_chunk tiles a carry step (stage_common.h's block_scan_in_place).
 __global__ __launch_bounds__(WN_SCAN_BLOCK) void window_scan_kernel(WnArgs a) {
   __shared__ uint64_t wsum[WN_SCAN_BLOCK / 64];
   if (threadIdx.x < WN_S_WORDS) a.ctr[threadIdx.x] = 0;
   uint64_t m, total;
   if (!wn_counts(a, &m, &total)) return;
-  const uint64_t tiles = wn_tiles_eff(total);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t chunk = a.scan_chunk && a.scan_chunk < WN_SCAN_BLOCK ? a.scan_chunk : WN_SCAN_BLOCK;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < tiles; base += chunk) {
-    const uint64_t t = base + threadIdx.x;
-    const bool mine = threadIdx.x < chunk && t < tiles;
-    const uint64_t x = mine ? a.tile_tot[t] : 0ull;
-    uint64_t incl = x;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < WN_SCAN_BLOCK / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    if (mine) a.tile_tot[t] = carry + before + incl - x;
-    carry += all;
-    __syncthreads();
-  }
+  (void)block_scan_in_place<WN_SCAN_BLOCK>(a.tile_tot, a.tile_tot, wn_tiles_eff(total), wsum,
+                                           scan_chunk_of<WN_SCAN_BLOCK>(a.scan_chunk));
 }
 
 __device__ inline WnRec wn_load_rec(const WnRec* p) {
@@ -228,24 +185,9 @@ __device__ inline WnPlan wn_inbox(const WnArgs& a, uint64_t k, uint32_t A, uint3
   return p;
 }
 
-// The block's sums into the counters: a wave's by shuffles, the waves' through LDS, one atomic a
-// counter.  Every thread of the block calls it.
+// The block's sums into the counters.  Every thread of the block calls it.
 __device__ inline void wn_report(const WnArgs& a, const WnAcc& acc) {
-  __shared__ unsigned long long red[5];
-  __shared__ uint32_t red_bad;
-  if (threadIdx.x < 5) red[threadIdx.x] = 0;
-  if (threadIdx.x == 0) red_bad = 0;
-  __syncthreads();
-#pragma unroll
-  for (uint32_t c = 0; c < 5; ++c) {
-    uint64_t s = acc.v[c];
-    for (uint32_t d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&red[c], static_cast<unsigned long long>(s));
-  }
-  if (__any(acc.bad) && (threadIdx.x & 63u) == 0) atomicOr(&red_bad, 1u);
-  __syncthreads();
-  if (threadIdx.x < 5 && red[threadIdx.x]) atomicAdd(a.ctr + WN_S_SENDS + threadIdx.x, red[threadIdx.x]);
-  if (threadIdx.x == 5 && red_bad) atomicOr(a.ctr + WN_S_FLAGS, static_cast<unsigned long long>(WN_F_BAD_SUB));
+  block_report<5>(a.ctr, WN_S_SENDS, acc.v, acc.bad ? WN_F_BAD_SUB : 0u, WN_S_FLAGS);
 }
 
 __global__ __launch_bounds__(WN_BLOCK) void window_verdict_kernel(WnArgs a) {
@@ -270,8 +212,8 @@ __global__ __launch_bounds__(WN_BLOCK) void window_verdict_kernel(WnArgs a) {
     __syncthreads();
     // the inboxes whose head lies in the tile: one with deliveries marks its head; one without
     // has no delivery that would need its plan and is finished here
-    const uint64_t k_lo = wn_lower(a.inbox_offsets, m, ts);
-    const uint64_t k_hi = last ? m : wn_lower(a.inbox_offsets, m, ts + WN_TILE);
+    const uint64_t k_lo = csr_lower(a.inbox_offsets, 0, m, ts);
+    const uint64_t k_hi = last ? m : csr_lower(a.inbox_offsets, 0, m, ts + WN_TILE);
     for (uint64_t k = k_lo + threadIdx.x; k < k_hi; k += WN_BLOCK) {
       const uint64_t off = a.inbox_offsets[k], nxt = a.inbox_offsets[k + 1];
       const uint64_t p = off < total ? off : total, pn = nxt < total ? nxt : total;
@@ -285,13 +227,13 @@ __global__ __launch_bounds__(WN_BLOCK) void window_verdict_kernel(WnArgs a) {
     for (uint32_t j = 0; j < WN_ROWS; ++j) hv[j] = hk[threadIdx.x * WN_ROWS + j];
     if (threadIdx.x == 0 && hv[0] == 0 && valid) {
       // the inbox that reaches into the tile: the last one whose head is at or before ts
-      hv[0] = static_cast<uint32_t>(wn_lower(a.inbox_offsets, m, ts + 1));
+      hv[0] = static_cast<uint32_t>(csr_lower(a.inbox_offsets, 0, m, ts + 1));
     }
     uint64_t x = 0;
 #pragma unroll
     for (uint32_t j = 0; j < WN_ROWS; ++j) x += wn_indicator(o[j]) + (hv[j] ? WN_ONE_H : 0ull);
     uint64_t all;
-    const uint64_t excl = wn_block_scan(x, wsum, &all);  // (its first barrier: every hk has been read)
+    const uint64_t excl = block_excl_scan<WN_BLOCK>(x, wsum, &all);  // (its first barrier: every hk has been read)
     {
       uint64_t run = excl;
 #pragma unroll
