@@ -110,6 +110,12 @@ RETRY_EXPORTS = (
     "emqx_retry_stamp_batch_device_async", "emqx_retry_stamp_host", "emqx_retry_sweep_batch", "emqx_retry_sweep_batch_device",
     "emqx_retry_sweep_batch_device_async", "emqx_retry_sweep_host", "emqx_retry_set_tuning", "emqx_retry_stats_get",
 )
+# Every symbol include/emqx_mqueue.h declares (queued messages and dequeue/1 per session).
+MQUEUE_EXPORTS = (
+    "emqx_mqueue_create", "emqx_mqueue_destroy", "emqx_mqueue_reserve", "emqx_mqueue_put_batch", "emqx_mqueue_put_batch_device",
+    "emqx_mqueue_put_batch_device_async", "emqx_mqueue_put_host", "emqx_mqueue_take_batch", "emqx_mqueue_take_batch_device",
+    "emqx_mqueue_take_batch_device_async", "emqx_mqueue_take_host", "emqx_mqueue_set_tuning", "emqx_mqueue_stats_get",
+)
 # Every symbol include/emqx_route.h declares (dests, aggre/1 and forward lists per node).
 ROUTE_EXPORTS = (
     "emqx_routetab_create", "emqx_routetab_destroy", "emqx_routetab_add", "emqx_routetab_remove",
@@ -393,6 +399,46 @@ class RetryStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
 
 
+class MqueuePutArgs(ctypes.Structure):
+    """struct emqx_mqueue_put_args (include/emqx_mqueue.h): the buffers of one put call."""
+    _fields_ = [
+        ("inbox_subs", ctypes.c_void_p), ("inbox_offsets", ctypes.c_void_p), ("box_opts", ctypes.c_void_p),
+        ("n_boxes", ctypes.c_void_p),
+        ("m", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("verdicts", ctypes.c_void_p), ("refs", ctypes.c_void_p), ("sessions", ctypes.c_void_p),
+        ("ring", ctypes.c_void_p), ("heads", ctypes.c_void_p), ("q", ctypes.c_uint64), ("sub_limit", ctypes.c_uint64),
+        ("out_evicted", ctypes.c_void_p), ("out_unstored", ctypes.c_void_p),
+    ]
+
+
+class MqueueTakeArgs(ctypes.Structure):
+    """struct emqx_mqueue_take_args (include/emqx_mqueue.h): the buffers of one take call."""
+    _fields_ = [
+        ("subs", ctypes.c_void_p), ("n_boxes", ctypes.c_void_p), ("m", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("update_table", ctypes.c_uint64),
+        ("ring", ctypes.c_void_p), ("heads", ctypes.c_void_p), ("q", ctypes.c_uint64), ("now_ms", ctypes.c_uint64),
+        ("deadlines", ctypes.c_void_p), ("ref_limit", ctypes.c_uint64), ("cap_out", ctypes.c_uint64),
+        ("out_offsets", ctypes.c_void_p), ("out_opts", ctypes.c_void_p), ("out_verdicts", ctypes.c_void_p),
+        ("out_pkt_ids", ctypes.c_void_p), ("out_refs", ctypes.c_void_p), ("out_status", ctypes.c_void_p),
+        ("out_counts", ctypes.c_void_p),
+    ]
+
+
+class MqueueStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("calls", ctypes.c_uint64),
+        ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
 class RouteBatch(ctypes.Structure):
     """struct emqx_route_batch (include/emqx_route.h): the buffers of one route call."""
     _fields_ = [
@@ -617,6 +663,19 @@ def lib():
         "emqx_retry_sweep_host": (i32, [vp, ctypes.POINTER(RetrySweepArgs), vp]),
         "emqx_retry_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_retry_stats_get": (i32, [vp, ctypes.POINTER(RetryStats)]),
+        "emqx_mqueue_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_mqueue_destroy": (i32, [vp]),
+        "emqx_mqueue_reserve": (i32, [vp, u64, u64]),
+        "emqx_mqueue_put_batch": (i32, [vp, ctypes.POINTER(MqueuePutArgs), vp]),
+        "emqx_mqueue_put_batch_device": (i32, [vp, ctypes.POINTER(MqueuePutArgs), vp, vp]),
+        "emqx_mqueue_put_batch_device_async": (i32, [vp, ctypes.POINTER(MqueuePutArgs), vp, vp]),
+        "emqx_mqueue_put_host": (i32, [vp, ctypes.POINTER(MqueuePutArgs), vp]),
+        "emqx_mqueue_take_batch": (i32, [vp, ctypes.POINTER(MqueueTakeArgs), vp]),
+        "emqx_mqueue_take_batch_device": (i32, [vp, ctypes.POINTER(MqueueTakeArgs), vp, vp]),
+        "emqx_mqueue_take_batch_device_async": (i32, [vp, ctypes.POINTER(MqueueTakeArgs), vp, vp]),
+        "emqx_mqueue_take_host": (i32, [vp, ctypes.POINTER(MqueueTakeArgs), vp]),
+        "emqx_mqueue_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_mqueue_stats_get": (i32, [vp, ctypes.POINTER(MqueueStats)]),
         "emqx_routetab_create": (i32, [ctypes.c_int32, u32, ctypes.POINTER(vp)]),
         "emqx_routetab_destroy": (i32, [vp]),
         "emqx_routetab_add": (i32, [vp, vp, vp, vp, u64]),

@@ -71,10 +71,11 @@
  * per-slot minima (emqx_amd/csrc/ack.h), and the time of a call does not depend on how the acks
  * are spread over the sessions.
  *
- * Out of scope, kept by the caller: the mqueue's contents and emqx_mqueue:out/1 (the stage gives
- * `room`; the caller pops that many non-QoS-0 messages and feeds them to the window stage as an
- * inbox: dequeue/1 ends in the same deliver/3 fold), awaiting_rel and the inbound QoS 2 path
- * (publish/3, pubrel/2), latency stats, a NIF binding.  The timestamps of the entries, retry/1 with
+ * Out of scope, kept by the caller: awaiting_rel and the inbound QoS 2 path (publish/3, pubrel/2),
+ * latency stats, a NIF binding.  The dequeue/1 that follows an ack is the mqueue stage's
+ * (emqx_mqueue.h): its take call runs behind the run call on the stream, reads the lowered
+ * `inflight` and pops what `room` allows; its outputs are inputs of the record call, which needs no
+ * change for it.  The timestamps of the entries, retry/1 with
  * message expiry and replay/1 are the retry stage's (emqx_retry.h): it keeps a stamp per slot next
  * to slots[] and is called behind every record and run call.
  *

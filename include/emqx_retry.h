@@ -76,15 +76,14 @@
  * (pkt_id, slot index) order, EMQX_RETRY_PUBREL for PUBREL_AWAIT and EMQX_RETRY_PUBLISH_DUP for
  * anything else; no expiry check, every timer EMQX_RETRY_NO_TIMER, nothing written but the outputs.
  * stamps, intervals and deadlines are not read and may be NULL.  replay/1's trailing dequeue/1 is
- * the caller's, as `room` is in emqx_ack.h.
+ * emqx_mqueue_take_* (emqx_mqueue.h) on the same stream.
  *
  * No thread walks a list: per slot the fold is a predicate, per item a rank among at most W keys,
  * per session one minimum (emqx_amd/csrc/retry.h).
  *
  * Out of scope, kept by the caller: awaiting_rel and the inbound QoS 2 path (publish/3, pubrel/2,
- * expire(awaiting_rel, _)), the mqueue's contents and dequeue/1, check_expire_latency and the
- * latency stats, timer wheels (the caller decides which sessions are due, or sweeps them all), a
- * NIF binding.
+ * expire(awaiting_rel, _)), check_expire_latency and the latency stats, timer wheels (the caller
+ * decides which sessions are due, or sweeps them all), a NIF binding.
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_ack.h: the calls
  * on one handle share its device scratch and are ordered by the handle.

@@ -70,9 +70,10 @@
  *
  * Out of scope, kept by the caller: priority tables (p_table; mark such sessions PASS), the
  * shared-subscription ack and nack path (maybe_ack / maybe_nack, off by default), message expiry,
- * active_n slicing of an inbox, the ack-driven dequeue/1 and retry, which ids are still inflight
- * (only the count is modelled; emqx_ack.h keeps the ids and takes the acks), the id-to-pid lookup
- * and the send.
+ * active_n slicing of an inbox, which ids are still inflight (only the count is modelled;
+ * emqx_ack.h keeps the ids and takes the acks, emqx_retry.h their ages), the id-to-pid lookup and
+ * the send.  The queued messages themselves and the ack-driven dequeue/1 are the mqueue stage's
+ * (emqx_mqueue.h): its put call runs behind this one and stores what the verdicts queue.
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_inbox.h: the
  * calls on one handle share its device scratch and are ordered by the handle.
