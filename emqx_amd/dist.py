@@ -451,6 +451,8 @@ class _HostEngine:
         offs = np.ctypeslib.as_array((ctypes.c_uint64 * (n + 1)).from_address(o_addr)).astype(np.int64)
         lo, hi = int(offs[0]), int(offs[-1])  # (a batch matched in place starts past its chunk's header)
         buf = np.ctypeslib.as_array((ctypes.c_uint8 * max(hi, 1)).from_address(b_addr))[lo:hi]
+        if hi == lo:  # (only empty topics: bytes nobody reads, so the function never sees a null buffer)
+            buf = np.zeros(16, np.uint8)
         cnt, ids = self.fn(self.slot, torch.from_numpy(buf.copy()), torch.from_numpy(offs - offs[0]))
         cnt = cnt.numpy().astype(np.int64)
         out = np.ctypeslib.as_array((ctypes.c_uint64 * (n + 1)).from_address(off_addr))
@@ -513,6 +515,7 @@ class ShardedMatcher:
         caller computed them already (both are functions of the filters and the world).
         ``p_space``: the plan's space-P layout (``shard_plan``)."""
         self.group = group
+        self._no_group = rank_world is not None  # (a rank of an EmulatedWorld: never a collective)
         if rank_world is not None:
             self.rank, self.world = rank_world
         else:
@@ -570,8 +573,23 @@ class ShardedMatcher:
         self._ids_floor = 1 << 16  # (an engine call's id buffer is never smaller; tests lower it)
         self._fixed = None        # the fixed form's agreed capacities (_learn_fixed)
         self._last_sizes = None   # the last classic step's sizes (what _learn_fixed learns from)
+        self._last_slots = None   # ... and its slot batches (byte address, offsets, requests)
         self.last_fixed_redo = 0
         self.last_fixed_enqueue_ms = 0.0
+        self._pad_ids = self._learn_pad_ids()
+
+    def _learn_pad_ids(self) -> List[int]:
+        """Per slot the ids its matcher returns for one empty topic (the root-wildcard filters
+        '#', '+', '+/#', '/#' and '' it holds): what every padding topic of a fixed-form batch
+        adds to the slot's engine output (``_step_gen_fixed`` gives the id buffer that room)."""
+        tb = torch.zeros(16, dtype=torch.uint8, device=self.device)
+        to = torch.zeros(2, dtype=torch.int64, device=self.device)
+        caps = list(self._caps)
+        try:
+            return [0 if self.engines[e] is None else int(self._engine_csr(e, tb, to)[1].numel())
+                    for e in range(SHARD_ENGINES)]
+        finally:
+            self._caps = caps  # (_engine_csr learns capacities; one empty topic teaches none)
 
     # (the step's resources are the current lane's)
     _step = property(lambda self: self._lane.step)
@@ -983,6 +1001,7 @@ class ShardedMatcher:
                                           S), "emqx_shard_step_recv")
         mark(3)
         qaddr = [qb[e] for e in range(E)]
+        self._last_slots = [(qaddr[e], qoff[e], NQ[e]) for e in range(E)]  # (_teach_padding reads them)
         self.last_local_topics = sum(NQ)
         self.last_slot_topics = NQ
         # 2. the engines, asynchronously, into learnt capacities; each on a stream of its own
@@ -1056,7 +1075,9 @@ class ShardedMatcher:
         return out_off, out_ids[:total]
 
     def _allreduce_max(self, vals: List[int]) -> List[int]:
-        if self.world == 1 or self.group is None and not dist.is_initialized():
+        # (a rank with no process group agrees its maxima outside: EmulatedWorld.learn_fixed; the
+        # process may still have a default group, which is not this matcher's)
+        if self.world == 1 or self._no_group or self.group is None and not dist.is_initialized():
             return list(vals)
         on_dev = self._cuda and dist.get_backend(self.group) != "gloo"
         t = torch.tensor(vals, dtype=torch.int64, device=self.device if on_dev else "cpu")
@@ -1078,6 +1099,36 @@ class ShardedMatcher:
         q = [0 if self.engines[e] is None else max(old["q"][e], x + x // 128 + 2048) for e, x in enumerate(ls["q"])]
         y = [0 if self.engines[e] is None else max(old["y"][e], x + x // 64 + 65536) for e, x in enumerate(ls["y"])]
         self._fixed = {"chunk": c1, "answer": c2, "q": q, "y": y}
+        self._pad_ids = self._learn_pad_ids()  # (again: adopted engines may have gained root filters)
+        self._teach_padding()
+
+    def _teach_padding(self):
+        """The last classic step's slot batches once more, padded as the fixed form pads them
+        (empty topics up to the slot's capacity), through the engines' synchronous call.  An
+        engine sizes its per-tile scratch from the calls that overflowed it, and only the
+        synchronous call grows it: the asynchronous one of a step reports the overflow in its
+        summary, which flags a fixed step — whose classic redo, without padding, fits and would
+        teach nothing, so the next fixed step would be flagged again.  A tile of padding topics
+        under root wildcards, or of requests and padding, can need more than any tile of
+        requests; after this call the batch just redone fits in its fixed form too.  Nothing to
+        do where no padding topic has ids, or there is no padding (world 1, one request a topic)."""
+        fx, slots = self._fixed, self._last_slots
+        if slots is None or (self.world == 1 and self.engines[0] is None and self.engines[1] is None):
+            return
+        caps = list(self._caps)
+        blank = torch.zeros(16, dtype=torch.uint8, device=self.device)
+        try:
+            for e, (addr, qoff, nq) in enumerate(slots):
+                cq = int(fx["q"][e])
+                if self.engines[e] is None or not self._pad_ids[e] or nq >= cq:
+                    continue
+                if nq:
+                    to = torch.cat([qoff[: nq + 1], qoff[nq: nq + 1].expand(cq - nq)])
+                else:  # (a slot no source asked: padding only)
+                    addr, to = blank.data_ptr(), torch.zeros(cq + 1, dtype=torch.int64, device=self.device)
+                self._engine_csr(e, addr, to, n=cq)
+        finally:
+            self._caps = caps  # (the requests' ids alone teach _caps: the padding's have their own room)
 
     def _step_gen_fixed(self, topics: Tuple[torch.Tensor, torch.Tensor], flag_addr: int):
         """One step in the fixed-capacity form (``emqx_shard_step_*_fixed``): the same kernels
@@ -1103,8 +1154,13 @@ class ShardedMatcher:
             tb = torch.zeros(16, dtype=torch.uint8, device=dev)
         n = to.numel() - 1
         c1, c2, capq, capy = fx["chunk"], fx["answer"], list(fx["q"]), fx["y"]
+        # a padding topic is an empty topic, and the root-wildcard filters match it: each adds
+        # _pad_ids[e] ids behind the requests' ids, which get room of their own (so a step whose
+        # requests' ids fit _caps is never flagged for its padding)
+        pad_room = [self._pad_ids[e] * capq[e] for e in range(E)]
         if G == 1 and self.engines[0] is None and self.engines[1] is None:
             capq[2] = n  # (world 1, one request a topic: at most n requests, so no padding)
+            pad_room[2] = 0
         send = self._buf("fsend", G * c1, torch.uint8)
         meta = self._buf("fmeta", (1 + 2 * E) * G, torch.int64)
         _lib.check(L.emqx_shard_step_send_fixed(st, P(tb), P(to), n, P(send), c1, P(meta), S),
@@ -1124,7 +1180,7 @@ class ShardedMatcher:
             if not capq[e]:
                 outs.append([ro, self._buf(f"ids{e}", 16, torch.int32)])
                 continue
-            ri = self._buf(f"ids{e}", max(self._caps[e], self._ids_floor), torch.int32)
+            ri = self._buf(f"ids{e}", max(self._caps[e], self._ids_floor) + pad_room[e], torch.int32)
             room += ri.numel()
             es = cur if not used or not self._cuda else self._engine_stream(len(used) - 1)
             if self._cuda and self._lane.stream_e is not None and cur is not None and cur == self._lane.stream_hi:

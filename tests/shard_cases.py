@@ -25,6 +25,11 @@ kOneBlockScan = 8192, else segments of kScanSeg = 2048; recv and answer grids ca
   large           world 64, 1,100,000 topics: N = 829,321, 405 segments (per = 2 in
                   shard_seg_scan_kernel), 2.2 M requests (> 2,097,152: shard_gather_kernel's
                   second trip), n > 524,288 (shard_merge_kernel's)
+  fixed3, fixed64 world 3 (1,500 topics a source) and 64 (300 a source) in the fixed form (FIXED_CASES:
+                  exact capacities, one capacity too small, a bad summary, and capacities with padding
+                  topics behind the requests: 0, 1, 17 and more than a pass of the recv grid,
+                  without ids and with marked ids of their own, pad_extras)
+  fixed3_sparse   world 3, 8 topics from two sources: slots no source asks, with padding only
 """
 
 import ctypes
@@ -159,6 +164,8 @@ def case(name):  # noqa: C901
         return Case(name, 3, EMPTY_PLAN, [rt(1500, 40 + s) for s in range(3)])
     if name == "fixed64":
         return Case(name, 64, EMPTY_PLAN, [rt(300, 50 + s) for s in range(64)])
+    if name == "fixed3_sparse":  # a small batch after a large one: slots with capacity and no request
+        return Case(name, 3, EMPTY_PLAN, _sources(3, {0: numbered_topics(7, b"zz%d/y"), 2: pack([b"solo"])}))
     raise KeyError(name)
 
 
@@ -326,12 +333,13 @@ class World:
                     assert 0 <= at and at + len(eby) <= len(res.send[src[0]]), what
                     assert np.array_equal(res.send[src[0]][at: at + len(eby)], eby), what + " bytes"
                 else:
-                    assert got[0] == 0, what
+                    assert got[0] == 0 and got[ne] == len(eby), what  # (padding topics: empty, at the slot's end)
                     assert_sentinel(raw, len(eby), what + " bytes")
                     assert np.array_equal(raw[: len(eby)], eby), what + " bytes"
                 # 6. the synthetic matcher's CSR of the batch as read back, padded to the capacity
+                # (fixed["pad_ids"]: the padding topics have ids of their own behind the requests')
                 off, ids = R.synth_csr(r, e, eby, eoff)
-                off = np.concatenate([off, np.full(capq[e] - ne, off[ne], np.uint64)])
+                off, ids = R.pad_csr(off, ids, capq[e] - ne, bool(fixed and fixed.get("pad_ids")))
                 csrs.append((self.buf(data=off), self.buf(data=ids), off, ids))
             n_ids = sum(len(c[3]) for c in csrs)
             n_q = sum(len(c[2]) - 1 for c in csrs)
@@ -446,7 +454,7 @@ def run_case(c, device, world=None):
 
 # ---- the fixed form's cases ------------------------------------------------------------------------
 
-FIXED_CASES = ("fits", "chunk_small", "slot_small", "answer_small", "summary_bad")
+FIXED_CASES = ("fits", "chunk_small", "slot_small", "answer_small", "summary_bad", "padded", "padded_ids")
 
 
 def fixed_caps(c, kind):
@@ -467,13 +475,42 @@ def fixed_caps(c, kind):
         fx["chunk_words"] -= 1
     elif kind == "summary_bad":
         fx["bad"] = (2,)
+    elif kind in ("padded", "padded_ids"):
+        extra = pad_extras(c)
+        fx["capq"] = [[fx["capq"][r][e] + extra[r][e] for e in range(E)] for r in range(G)]
+        fx["capy"] = [[fx["capy"][r][e] + 16 * ((r + 2 * e) % 4) for e in range(E)] for r in range(G)]
+        fx["pad_ids"] = kind == "padded_ids"
     else:
         assert kind == "fits"
     return fx
 
 
+PAD_EXTRA = (0, 1, 17)
+PAD_LONG = (1, 0)  # the (rank, slot) padded over one pass of the recv grid
+
+
+def pad_extras(c):
+    """Padding topics per (rank, slot) of the `padded` kinds: 0, 1 or 17 by (rank + slot) % 3, so
+    every rank has each and no two neighbours agree; rank 1's slot 0 gets more than one pass of
+    shard_recv_fixed_kernel's grid: the smallest 512 * 2^k above the grid's stride, which is
+    computed (shard_ref.recv_stride) from the rank's capacities with that padding in them, so the
+    padding block's threads write at k and k + stride (pad_slot's second trip)."""
+    ref, G = c.ref, c.world
+    extra = [[PAD_EXTRA[(r + e) % 3] for e in range(E)] for r in range(G)]
+    r, e = PAD_LONG
+    need_q = [int(ref.q0(r, k)[G]) for k in range(E)]
+    capy = [len(ref.slot_batch(r, k)[1]) + 16 * ((r + 2 * k) % 4) for k in range(E)]
+    long = 512
+    while True:
+        extra[r][e] = long
+        if long > R.recv_stride(G, [need_q[k] + extra[r][k] for k in range(E)], capy):
+            return extra
+        long *= 2
+
+
 def expected_fixed_flag(kind):
-    return {"fits": 0, "chunk_small": 1, "slot_small": 2, "answer_small": 8, "summary_bad": 4}[kind]
+    return {"fits": 0, "chunk_small": 1, "slot_small": 2, "answer_small": 8, "summary_bad": 4, "padded": 0,
+            "padded_ids": 0}[kind]
 
 
 def run_fixed(c, kind, device):
@@ -506,4 +543,28 @@ def run_fixed(c, kind, device):
         assert recv_f[1] == 2 and ans_f[1] == 2 and sum(1 for f in recv_f if f) == 1
     if kind == "fits":
         assert all(f == 0 for f in res.flags)
+    if kind in ("padded", "padded_ids"):
+        # padding costs no answer word and leaves no trace: every send buffer, answer chunk and
+        # CSR is the `fits` run's byte for byte (recv's padding offsets and the sentinel behind
+        # them are checked in World.step), and no padding id is in any of them
+        assert all(f == 0 for f in res.flags)
+        extra = pad_extras(c)
+        npad = sum(map(sum, extra))
+        assert extra[PAD_LONG[0]][PAD_LONG[1]] > R.recv_stride(G, fx["capq"][PAD_LONG[0]], fx["capy"][PAD_LONG[0]]) \
+            and {0, 1, 17} <= {x for row in extra for x in row}
+        same_bytes(res, fits_run(c, device))
+        for r in range(G):
+            assert not (res.answer[r] >> 24 == R.PAD_MARK).any(), "a padding id in an answer chunk of rank %d" % r
+            assert not (res.csr[r][1] >> 24 == R.PAD_MARK).any(), "a padding id in the CSR of source %d" % r
     return res
+
+
+@functools.lru_cache(maxsize=None)
+def fits_run(c, device):
+    """Case c's `fits` run on `device`, once for every padded kind compared with it."""
+    return run_fixed(c, "fits", device)
+
+
+def padded_ids_total(c):
+    """The padding ids the synthetic matcher of `padded_ids` writes over all of case c's slots."""
+    return sum(int((np.arange(x) % 6).sum()) for row in pad_extras(c) for x in row)

@@ -92,6 +92,31 @@ def synth_csr(rank, slot, tbytes, offsets):
     return ooff, ids.astype(np.uint32)
 
 
+PAD_MARK = 0xFF  # top byte of a padding topic's ids; a request's is rank * 3 + slot <= 191 (world 64)
+
+
+def pad_csr(off, ids, npad, with_ids):
+    """A slot's CSR over its fixed-size batch, as an engine writes it: the requests' CSR (off,
+    ids), then npad padding topics.  Without ids every padding offset is the requests' end; with
+    them padding topic j has j % 6 ids PAD_MARK << 24 | j << 3 | k behind the requests' ids (an
+    empty topic under root-wildcard filters), which no answer chunk and no output may carry."""
+    j = np.arange(npad, dtype=np.int64)
+    cnt = j % 6 if with_ids else np.zeros(npad, np.int64)
+    end = np.uint64(off[-1]) + np.cumsum(cnt).astype(np.uint64)
+    k = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    marks = (np.uint32(PAD_MARK << 24) | (np.repeat(j, cnt).astype(np.uint32) << np.uint32(3)) | k.astype(np.uint32))
+    return np.concatenate([off, end]).astype(np.uint64), np.concatenate([ids, marks]).astype(np.uint32)
+
+
+def recv_stride(G, capq, capy):
+    """The grid-stride of shard_recv_fixed_kernel for a rank's slot capacities, restating the
+    sizing of emqx_shard_step_recv_fixed: per = max(requests, bytes / 16) / (3 G) + 1 items a
+    (source, slot) part, x = per / 256 blocks rounded up, at most max(1, 1024 / G), of 256 threads."""
+    per = max(sum(capq), sum(capy) // 16) // (E * G) + 1
+    x = max(1, min((per + 255) // 256, max(1, 1024 // G)))
+    return 256 * x
+
+
 class Send:
     """One source's send: its requests sorted by key, the meta words and the send buffer."""
 

@@ -294,6 +294,134 @@ def test_sharded_fixed_capacity_steps(world, p_space):
             assert C.csr_mismatches(off, ids, off_o, ids_o).size == 0, (rank, k)
 
 
+ROOT_FILTERS = [b"#", b"+", b"+/#", b"/#", b""]  # every filter that matches the empty topic
+
+
+def _padding_workload(roots):
+    """(filters, batch A, batch B): config B's generator (20 K filters), with or without the root
+    filters; A = 6,000 '$' topics that match nothing (they teach the fixed form large slot
+    capacities and no ids), B = 10 topics that match only root filters."""
+    from emqx_amd import workloads as W
+    from emqx_amd.engine import pack
+    wl = W.config_b(n_filters=20_000, n_topics=10, seed=7)
+    have = set(W.unpack(wl.filters))
+    more = [f for f in ROOT_FILTERS if f not in have] if roots else []
+    nb = int(wl.filters[1][-1])
+    filters = (np.concatenate([wl.filters[0][:nb], np.frombuffer(b"".join(more), np.uint8)]),
+               np.concatenate([wl.filters[1].astype(np.uint64),
+                               nb + np.cumsum([len(x) for x in more]).astype(np.uint64)]))
+    A = pack([b"$q%d/x" % i for i in range(6000)])
+    B = pack([b"zz%d/y" % i for i in range(10)])
+    return filters, A, B
+
+
+def _worker_padding(rank, world, port, q, p_space, roots):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        filters, A, B = _padding_workload(roots)
+        sm = _matcher(filters, rank, world, p_space)
+        sm._caps, sm._ids_floor = [1, 1, 1], 1024
+        T = lambda b: (torch.from_numpy(b[0].copy()), torch.from_numpy(b[1].astype(np.int64)))  # noqa: E731
+        redo, res = [], []
+        for call in ([A, B, B, B], [B] * 4, [B] * 4, [B] * 4):
+            res += sm.match_stream([T(b) for b in call], fixed=True)
+            redo.append(sm.last_fixed_redo)
+        q.put((rank, redo, [(o.numpy(), i.numpy()) for o, i in res], list(sm._caps)))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("world,p_space,roots", [(2, "sharded", True), (3, "replicated", True),
+                                                 (2, "sharded", False), (3, "replicated", False)])
+def test_sharded_fixed_padding_converges(world, p_space, roots):
+    """The fixed form's padding topics are empty topics, and '#', '+', '+/#', '/#' and '' (the
+    oracle and shard_plan take the empty filter as any other) match the empty topic ('#', '+',
+    '+/#' on every rank, the other two on the rank of the empty first level): a slot learnt at 6,000 requests pads a 10-topic batch with thousands of topics of up to
+    five ids each, many times the 1 K ids the engines are given here.  A step whose requests' ids
+    fit is not flagged for that: after [A, B, B, B] the three calls [B] * 4 are redone at most
+    twice in all (a condition, not a measurement: the control without root filters needs no redo)
+    and the last two never; every step's CSR equals the single-table oracle's.
+
+    Before the id buffers had room for the padding's ids this failed with redo counts 3, 4, 4, 4
+    on every rank (every fixed step flagged, for ever); the control gave 0, 0, 0, 0."""
+    from oracle import cpp as C
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_padding, args=(r, world, port, q, p_space, roots)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = [q.get(timeout=240) for _ in range(world)]
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    filters, A, B = _padding_workload(roots)
+    o = C.CppOracle(True)
+    o.add_packed(*filters)
+    want = {id(b): o.match_csr(b[0], b[1].astype(np.uint64), mode=0, threads=2)[:2] for b in (A, B)}
+    assert int(want[id(A)][0][-1]) == 0
+    assert int(want[id(B)][0][-1]) == (10 * 2 if roots else 0)  # ('#' and '+/#')
+    # what a padding topic costs: the empty topic matches every root filter, the empty one included
+    pad_ids = int(o.match_csr(np.zeros(1, np.uint8), np.zeros(2, np.uint64), mode=0)[0][-1])
+    assert pad_ids == (len(ROOT_FILTERS) if roots else 0)
+    batches = [A, B, B, B] + [B] * 12
+    for rank, redo, res, caps in got:
+        print("world %d %s roots %s rank %d: last_fixed_redo %s" % (world, p_space, roots, rank, redo))
+        assert len(res) == len(batches)
+        assert max(caps) < 8192, caps  # (the requests' ids never needed more: padding teaches _caps nothing)
+        for k, (b, (off, ids)) in enumerate(zip(batches, res)):
+            assert C.csr_mismatches(off, ids, *want[id(b)]).size == 0, (rank, k)
+        if roots:
+            assert redo[2] == 0 and redo[3] == 0 and sum(redo) <= 2, (rank, redo)
+        else:
+            assert redo == [0, 0, 0, 0], (rank, redo)
+
+
+def _worker_no_group(port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        from emqx_amd import dist as D
+        filters = _padding_workload(True)[0]
+        plan = D.shard_plan(filters, 2)
+        sm = D.ShardedMatcher(filters, device=torch.device("cpu"), rank_world=(0, 2), plan=plan,
+                              match_fn=_oracle_match_fn(D.shard_engines(filters, 0, 2, plan)))
+        sm._last_sizes = {"chunk": 6400, "answer": 3200, "q": [128, 256, 384], "y": [640, 1280, 1920]}
+
+        def no_collective(*a, **k):
+            raise AssertionError("a rank_world matcher issued a collective")
+        for name in ("all_reduce", "all_to_all_single", "all_to_all", "all_gather", "broadcast"):
+            setattr(D.dist, name, no_collective)
+        sm._learn_fixed()
+        q.put(sm._fixed)
+    except BaseException as e:  # (the parent fails on it at once instead of waiting for a result)
+        q.put(repr(e))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(120)
+def test_rank_world_matcher_issues_no_collective():
+    """A matcher built with rank_world (a rank of an EmulatedWorld: world 2, no group) in a
+    process that has a default group of its own: _learn_fixed keeps the rank's own maxima and
+    issues no collective (the caller agrees the chunk capacities, EmulatedWorld.learn_fixed)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_worker_no_group, args=(_free_port(), q))
+    p.start()
+    fixed = q.get(timeout=100)
+    p.join(60)
+    assert p.exitcode == 0
+    assert fixed == {"chunk": (6400 + 100 + 4096 + 15) // 16 * 16, "answer": 3200 + 100 + 16384,
+                     "q": [128 + 1 + 2048, 256 + 2 + 2048, 384 + 3 + 2048],
+                     "y": [640 + 10 + 65536, 1280 + 20 + 65536, 1920 + 30 + 65536]}
+
+
 def test_shard_layout_covers_every_match():
     """Every filter that matches a topic is held by the rank of the topic's request to the
     filter's engine (so the two requests find every match, once); a filter is held by exactly

@@ -304,3 +304,67 @@ def test_emulated_world_every_source_id_for_id(world, p_space):
                 _check(got, wl.filters, srcs[r])
     finally:
         ew.close()
+
+
+@pytest.mark.parametrize("world,p_space", [(2, "sharded"), (3, "sharded"), (3, "replicated")])
+def test_emulated_world_fixed_padding_under_root_wildcards(world, p_space):
+    """A small batch after a large one in the fixed form, on real engines: the slots learnt at
+    thousands of requests pad a 10-topic batch with thousands of empty topics, each matched by
+    '#', '+', '+/#' (and '/#' on one rank) — several times the id room the requests are given here
+    (a 1 K floor, ~4 K learnt).  The padding's ids have room of their own: no step is flagged
+    (EmulatedWorld.step and rank_stream raise on a flagged step), and every source's CSR is the
+    oracle's ID for ID.
+
+    Then a batch whose topics match more: a 64-topic tile of its last requests and padding needs
+    more of the engine's per-tile scratch (263 entries at world 2) than any tile of requests, or
+    the 256 a workspace starts with.  Only an engine's synchronous call grows that scratch, so
+    what a flagged step's redo does is done here — the classic step, then learn_fixed, which
+    walks the padded batch once (_teach_padding) — after which the fixed form is not flagged."""
+    import torch
+    from emqx_amd.dist import EmulatedWorld
+    from emqx_amd.engine import pack
+    from emqx_amd.workloads import take
+    dev = torch.device("cuda:0")
+    filters = pack(FILTERS + [b"/#"] + [b"+/k%d/z" % i for i in range(12)])  # (some '+/x' filters on every rank)
+    large = [pack([b"$q%d_%d/x" % (s, i) for i in range(6000)]) for s in range(world)]  # (no match: no ids learnt)
+    small = [pack([b"zz%d_%d/y" % (s, i) for i in range(10)]) for s in range(world)]  # (root wildcards only)
+    mixed = [pack([b"zz%d_%d/y" % (s, i) for i in range(10)] + TOPICS[s::6]) for s in range(world)]
+    ew = EmulatedWorld(filters, world, dev, p_space=p_space)
+    try:
+        assert all(x[2] > 0 and (p_space == "replicated" or min(x) > 0) for x in ew.filters_per_rank)
+        for m in ew.matchers:
+            m._caps, m._ids_floor = [1, 1, 1], 1024
+        res = ew.step([_dev_topics(b) for b in large])
+        for s in range(world):
+            assert _check(res[s], filters, large[s]) == 0
+        ew.learn_fixed()
+        for m in ew.matchers:
+            for ln in m._lanes:
+                for e in range(3):
+                    ln.bufs.pop(f"ids{e}", None)
+            # what one empty topic matches on each of the rank's engines, by the oracle over the
+            # engine's own filters ('#', '+', '+/#' on every rank; '/#' on the rank of the level '')
+            want = [0 if m.engines[e] is None else
+                    int(_oracle(take(filters, m.local_ids[e]), (np.zeros(1, np.uint8), np.zeros(2, np.uint64)))[0][-1])
+                    for e in range(3)]
+            assert m._pad_ids == want and want[2] in (3, 4) and max(m._caps) < 8192, (m._pad_ids, want)
+            # (not vacuous: some slot's padding alone is over the room its requests' ids have)
+            assert any(m._pad_ids[e] * m._fixed["q"][e] > 2 * max(m._caps[e], m._ids_floor) for e in range(3))
+        assert sorted(m._pad_ids[2] for m in ew.matchers) == [3] * (world - 1) + [4]
+        for batches, least in ((small, 40), (mixed, 58)):  # (ids a source by the oracle: 40; 58 to 63)
+            if batches is mixed:  # (the redo of a flagged step: classic, and the capacities learnt again)
+                res = ew.step([_dev_topics(b) for b in batches])
+                for s in range(world):
+                    _check(res[s], filters, batches[s])
+                ew.learn_fixed()
+                assert all(max(m._caps) < 8192 for m in ew.matchers)  # (the padded walk taught _caps nothing)
+            res = ew.step([_dev_topics(b) for b in batches], fixed=True)
+            for s in range(world):
+                assert _check(res[s], filters, batches[s]) >= least
+            for r in range(world):
+                ms, rs = ew.rank_stream(r, _dev_topics(batches[r]), 3, fixed=True)
+                assert len(rs) == 3
+                for got in rs:
+                    _check(got, filters, batches[r])
+    finally:
+        ew.close()

@@ -3,8 +3,10 @@
 wave_count and shard_sort_scatter_kernel see tens of distinct keys a wave; recv and answer grids
 capped at 16 blocks), the segmented sort scan (shard_seg_sums / seg_scan / seg_final, N > 8,192
 table entries) next to the largest one-block table, second trips of unpack_part, answer_source,
-shard_gather_kernel, shard_merge_kernel and shard_seg_scan_kernel, and the fixed form's flags at
-world > 1.  One process, no process group, no engines: tests/shard_cases.py drives the C API with
+shard_gather_kernel, shard_merge_kernel and shard_seg_scan_kernel, the fixed form's flags at
+world > 1, and its padding topics (slot capacities above the need: the padding block of
+shard_recv_fixed_kernel through a second trip, engine outputs that hold padding ids behind the
+requests').  One process, no process group, no engines: tests/shard_cases.py drives the C API with
 a synthetic matcher (its docstring lists the cases and the thresholds they sit on).
 
 Every case runs on the device against the sequential restatement (tests/shard_ref.py: meta words
@@ -84,3 +86,18 @@ def test_device_fixed_world3(kind):
 def test_device_fixed_fits_world64():
     c = SC.case("fixed64")
     SC.same_bytes(SC.run_fixed(c, "fits", 0), SC.run_fixed(c, "fits", -1))
+
+
+def test_device_fixed_padded_ids_world64():
+    """Padding topics with ids of their own at world 64 (the recv grid capped at 16 blocks: rank
+    1's slot 0 is padded over two of its passes): answers and CSRs are the `fits` run's."""
+    c = SC.case("fixed64")
+    SC.same_bytes(SC.run_fixed(c, "padded_ids", 0), SC.run_fixed(c, "padded_ids", -1))
+
+
+@pytest.mark.parametrize("kind", ("padded", "padded_ids"))
+def test_device_fixed_padded_sparse(kind):
+    """A small batch in large capacities: slots that hold padding topics only (what a rank's
+    engines walk after a large batch taught the capacities)."""
+    c = SC.case("fixed3_sparse")
+    SC.same_bytes(SC.run_fixed(c, kind, 0), SC.run_fixed(c, kind, -1))

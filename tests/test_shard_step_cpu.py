@@ -88,6 +88,43 @@ def test_host_mode_fixed_fits_world64():
     SC.run_fixed(SC.case("fixed64"), "fits", -1)
 
 
+def test_host_mode_fixed_padded_ids_world64():
+    SC.run_fixed(SC.case("fixed64"), "padded_ids", -1)
+
+
+def sparse_slots(c):
+    """The (rank, slot) pairs of case c that no source asks and that the padded kinds give topics."""
+    extra = SC.pad_extras(c)
+    return [(r, e) for r in range(c.world) for e in range(SC.E) if not c.ref.q0(r, e)[c.world] and extra[r][e]]
+
+
+@pytest.mark.parametrize("kind", ("padded", "padded_ids"))
+def test_host_mode_fixed_padded_sparse(kind):
+    """A small batch in large capacities (fixed3 and fixed64 leave no slot without requests): slots
+    that hold padding topics only."""
+    c = SC.case("fixed3_sparse")
+    assert len(sparse_slots(c)) >= 2
+    SC.run_fixed(c, kind, -1)
+
+
+def test_padded_shapes():
+    """The padded kinds' arithmetic: 0, 1 and 17 padding topics on every rank, and on rank 1's
+    slot 0 more than the recv grid's stride for that rank's capacities (a second trip of the
+    padding block); `padded_ids` gives the padding thousands of ids."""
+    for name, long in (("fixed3", 1024), ("fixed64", 512), ("fixed3_sparse", 512)):
+        c = SC.case(name)
+        extra = SC.pad_extras(c)
+        fx = SC.fixed_caps(c, "padded_ids")
+        r, e = SC.PAD_LONG
+        assert extra[r][e] == long > R.recv_stride(c.world, fx["capq"][r], fx["capy"][r]), name
+        assert all(sorted(row) == [0, 1, 17] for k, row in enumerate(extra) if k != r), name
+        assert all(y % 16 == 0 for y in np.subtract(fx["capy"], SC.fixed_caps(c, "fits")["capy"]).ravel())
+        assert SC.padded_ids_total(c) > 2 * long, name
+    assert R.recv_stride(3, [400_000, 0, 0], [0, 0, 0]) == 256 * 174  # (44,445 items a part)
+    assert R.recv_stride(3, [4_000_000, 0, 0], [0, 0, 0]) == 256 * 341  # the cap, 1024 / 3 blocks
+    assert R.recv_stride(64, [0, 0, 0], [16 * 192 * 300, 0, 0]) == 256 * 2  # sized by the bytes
+
+
 def test_host_mode_fixed_equals_classic():
     """`fits`: the fixed form's CSRs are the classic form's."""
     c = SC.case("fixed3")
