@@ -116,6 +116,12 @@ MQUEUE_EXPORTS = (
     "emqx_mqueue_put_batch_device_async", "emqx_mqueue_put_host", "emqx_mqueue_take_batch", "emqx_mqueue_take_batch_device",
     "emqx_mqueue_take_batch_device_async", "emqx_mqueue_take_host", "emqx_mqueue_set_tuning", "emqx_mqueue_stats_get",
 )
+# Every symbol include/emqx_rel.h declares (awaiting_rel, QoS 2 publish/3, pubrel/2 and expiry per session).
+REL_EXPORTS = (
+    "emqx_rel_create", "emqx_rel_destroy", "emqx_rel_reserve", "emqx_rel_run_batch", "emqx_rel_run_batch_device",
+    "emqx_rel_run_batch_device_async", "emqx_rel_run_host", "emqx_rel_expire_batch", "emqx_rel_expire_batch_device",
+    "emqx_rel_expire_batch_device_async", "emqx_rel_expire_host", "emqx_rel_set_tuning", "emqx_rel_stats_get",
+)
 # Every symbol include/emqx_route.h declares (dests, aggre/1 and forward lists per node).
 ROUTE_EXPORTS = (
     "emqx_routetab_create", "emqx_routetab_destroy", "emqx_routetab_add", "emqx_routetab_remove",
@@ -439,6 +445,47 @@ class MqueueStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
 
 
+class RelRunArgs(ctypes.Structure):
+    """struct emqx_rel_run_args (include/emqx_rel.h): the buffers of one run call."""
+    _fields_ = [
+        ("ev_subs", ctypes.c_void_p), ("ev_offsets", ctypes.c_void_p), ("events", ctypes.c_void_p),
+        ("n_boxes", ctypes.c_void_p),
+        ("m", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("ts", ctypes.c_void_p), ("src", ctypes.c_void_p), ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64),
+        ("rel", ctypes.c_void_p), ("w", ctypes.c_uint64), ("now_ms", ctypes.c_uint64),
+        ("max_awaiting", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("maxes", ctypes.c_void_p),
+        ("verdicts", ctypes.c_void_p), ("out_route", ctypes.c_void_p), ("out_counts", ctypes.c_void_p),
+        ("out_arm", ctypes.c_void_p),
+    ]
+
+
+class RelExpireArgs(ctypes.Structure):
+    """struct emqx_rel_expire_args (include/emqx_rel.h): the buffers of one expire call."""
+    _fields_ = [
+        ("subs", ctypes.c_void_p), ("n_boxes", ctypes.c_void_p), ("m", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("rel", ctypes.c_void_p), ("w", ctypes.c_uint64),
+        ("now_ms", ctypes.c_uint64), ("timeout_ms", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("timeouts", ctypes.c_void_p), ("channel_rule", ctypes.c_uint64),
+        ("out_status", ctypes.c_void_p), ("out_counts", ctypes.c_void_p),
+    ]
+
+
+class RelStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64), ("w", ctypes.c_uint64),
+        ("scratch_bytes", ctypes.c_uint64), ("lanes", ctypes.c_uint64), ("calls", ctypes.c_uint64),
+        ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
 class RouteBatch(ctypes.Structure):
     """struct emqx_route_batch (include/emqx_route.h): the buffers of one route call."""
     _fields_ = [
@@ -676,6 +723,19 @@ def lib():
         "emqx_mqueue_take_host": (i32, [vp, ctypes.POINTER(MqueueTakeArgs), vp]),
         "emqx_mqueue_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_mqueue_stats_get": (i32, [vp, ctypes.POINTER(MqueueStats)]),
+        "emqx_rel_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_rel_destroy": (i32, [vp]),
+        "emqx_rel_reserve": (i32, [vp, u64, u64, u64]),
+        "emqx_rel_run_batch": (i32, [vp, ctypes.POINTER(RelRunArgs), vp]),
+        "emqx_rel_run_batch_device": (i32, [vp, ctypes.POINTER(RelRunArgs), vp, vp]),
+        "emqx_rel_run_batch_device_async": (i32, [vp, ctypes.POINTER(RelRunArgs), vp, vp]),
+        "emqx_rel_run_host": (i32, [vp, ctypes.POINTER(RelRunArgs), vp]),
+        "emqx_rel_expire_batch": (i32, [vp, ctypes.POINTER(RelExpireArgs), vp]),
+        "emqx_rel_expire_batch_device": (i32, [vp, ctypes.POINTER(RelExpireArgs), vp, vp]),
+        "emqx_rel_expire_batch_device_async": (i32, [vp, ctypes.POINTER(RelExpireArgs), vp, vp]),
+        "emqx_rel_expire_host": (i32, [vp, ctypes.POINTER(RelExpireArgs), vp]),
+        "emqx_rel_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_rel_stats_get": (i32, [vp, ctypes.POINTER(RelStats)]),
         "emqx_routetab_create": (i32, [ctypes.c_int32, u32, ctypes.POINTER(vp)]),
         "emqx_routetab_destroy": (i32, [vp]),
         "emqx_routetab_add": (i32, [vp, vp, vp, vp, u64]),

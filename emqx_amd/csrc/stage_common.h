@@ -1,5 +1,5 @@
-// What the stages behind the match share (deliver, select, inbox, window, route, ack, retry;
-// DESIGN.md §3.9-§3.15): the bounded searches over a CSR's offsets, the wave and block scans, the
+// What the stages around the match share (deliver, select, inbox, window, route, ack, retry, mqueue
+// behind it and rel in front of it): the bounded searches over a CSR's offsets, the wave and block scans, the
 // one-block scan of the tile totals, the counter report and the guard of the C ABI.  The first part
 // is __host__ __device__ and compiles with a plain C++ compiler; the second is device code.
 #pragma once

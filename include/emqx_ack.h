@@ -71,8 +71,9 @@
  * per-slot minima (emqx_amd/csrc/ack.h), and the time of a call does not depend on how the acks
  * are spread over the sessions.
  *
- * Out of scope, kept by the caller: awaiting_rel and the inbound QoS 2 path (publish/3, pubrel/2),
- * latency stats, a NIF binding.  The dequeue/1 that follows an ack is the mqueue stage's
+ * Out of scope, kept by the caller: latency stats, a NIF binding.  awaiting_rel and the inbound
+ * QoS 2 path (publish/3, pubrel/2, expire(awaiting_rel, _)) are the rel stage's (emqx_rel.h), which
+ * keeps a table of its own next to slots[] and runs in front of the match.  The dequeue/1 that follows an ack is the mqueue stage's
  * (emqx_mqueue.h): its take call runs behind the run call on the stream, reads the lowered
  * `inflight` and pops what `room` allows; its outputs are inputs of the record call, which needs no
  * change for it.  The timestamps of the entries, retry/1 with

@@ -81,9 +81,10 @@
  * No thread walks a list: per slot the fold is a predicate, per item a rank among at most W keys,
  * per session one minimum (emqx_amd/csrc/retry.h).
  *
- * Out of scope, kept by the caller: awaiting_rel and the inbound QoS 2 path (publish/3, pubrel/2,
- * expire(awaiting_rel, _)), check_expire_latency and the latency stats, timer wheels (the caller
- * decides which sessions are due, or sweeps them all), a NIF binding.
+ * Out of scope, kept by the caller: check_expire_latency and the latency stats, timer wheels (the
+ * caller decides which sessions are due, or sweeps them all), a NIF binding.  awaiting_rel and the
+ * inbound QoS 2 path (publish/3, pubrel/2, expire(awaiting_rel, _)) are the rel stage's
+ * (emqx_rel.h).
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_ack.h: the calls
  * on one handle share its device scratch and are ordered by the handle.
