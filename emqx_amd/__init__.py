@@ -20,6 +20,8 @@ Modules mirror the reference's Erlang modules on the hot path:
                           redelivery lists in timestamp order, expired messages dropped, the next retry timer)
   :mod:`emqx_amd.mqueue`  emqx_mqueue in/2 + out/1, emqx_session dequeue/1 (the queued messages of every session in
                           device memory: what the window queued is stored, what an ack made room for is popped)
+  :mod:`emqx_amd.pmqueue` emqx_mqueue in/2 + out/1 with a p_table and shift_opts (the same for the sessions of a zone that
+                          sets mqueue_priorities: one ring per priority class, the order list and the credit per session)
   :mod:`emqx_amd.rel`     emqx_session publish/3 + pubrel/2 + expire(awaiting_rel, _) (which QoS 2 packet ids await their
                           PUBREL per session; an inbound batch against them: reason codes and the list to route)
   :mod:`emqx_amd.route`   emqx_broker aggre/1 + route/2 + do_route/2, emqx_router_helper cleanup_routes/1 (the route
@@ -38,5 +40,6 @@ from .window import Window  # noqa: F401,E402  (inflight and mqueue admission pe
 from .ack import Ack  # noqa: F401,E402  (inflight slots and PUBACK / PUBREC / PUBCOMP per session)
 from .retry import Retry  # noqa: F401,E402  (inflight ages, redelivery lists and timers per session)
 from .mqueue import Mqueue  # noqa: F401,E402  (queued messages and dequeue/1 per session)
+from .pmqueue import Pmqueue  # noqa: F401,E402  (the same with a priority table: per-class rings, order list, credit)
 from .rel import Rel  # noqa: F401,E402  (awaiting_rel, QoS 2 publish/3, pubrel/2 and expiry per session)
 from .route import ClusterRouter, RouteTable  # noqa: F401,E402  (dests, aggre/1 and forward lists per node)

@@ -116,6 +116,13 @@ MQUEUE_EXPORTS = (
     "emqx_mqueue_put_batch_device_async", "emqx_mqueue_put_host", "emqx_mqueue_take_batch", "emqx_mqueue_take_batch_device",
     "emqx_mqueue_take_batch_device_async", "emqx_mqueue_take_host", "emqx_mqueue_set_tuning", "emqx_mqueue_stats_get",
 )
+# Every symbol include/emqx_pmqueue.h declares (queued messages of sessions with a priority table).
+PMQUEUE_EXPORTS = (
+    "emqx_pmqueue_create", "emqx_pmqueue_destroy", "emqx_pmqueue_reserve", "emqx_pmqueue_put_batch", "emqx_pmqueue_take_batch",
+    "emqx_pmqueue_put_batch_device",
+    "emqx_pmqueue_put_batch_device_async", "emqx_pmqueue_put_host", "emqx_pmqueue_take_batch_device",
+    "emqx_pmqueue_take_batch_device_async", "emqx_pmqueue_take_host", "emqx_pmqueue_set_tuning", "emqx_pmqueue_stats_get",
+)
 # Every symbol include/emqx_rel.h declares (awaiting_rel, QoS 2 publish/3, pubrel/2 and expiry per session).
 REL_EXPORTS = (
     "emqx_rel_create", "emqx_rel_destroy", "emqx_rel_reserve", "emqx_rel_run_batch", "emqx_rel_run_batch_device",
@@ -445,6 +452,50 @@ class MqueueStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
 
 
+class PmqueuePutArgs(ctypes.Structure):
+    """struct emqx_pmqueue_put_args (include/emqx_pmqueue.h): the buffers of one put call."""
+    _fields_ = [
+        ("inbox_subs", ctypes.c_void_p), ("inbox_offsets", ctypes.c_void_p), ("box_opts", ctypes.c_void_p),
+        ("n_boxes", ctypes.c_void_p),
+        ("m", ctypes.c_uint64), ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("verdicts", ctypes.c_void_p), ("refs", ctypes.c_void_p), ("box_src", ctypes.c_void_p), ("msg_class", ctypes.c_void_p),
+        ("n_msgs", ctypes.c_uint64), ("tables", ctypes.c_void_p), ("n_tables", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("update_table", ctypes.c_uint64),
+        ("ring", ctypes.c_void_p), ("heads", ctypes.c_void_p), ("c", ctypes.c_uint64), ("qc", ctypes.c_uint64),
+        ("out_verdicts", ctypes.c_void_p), ("out_class", ctypes.c_void_p), ("out_evicted", ctypes.c_void_p),
+        ("out_counts", ctypes.c_void_p),
+    ]
+
+
+class PmqueueTakeArgs(ctypes.Structure):
+    """struct emqx_pmqueue_take_args (include/emqx_pmqueue.h): the buffers of one take call."""
+    _fields_ = [
+        ("subs", ctypes.c_void_p), ("n_boxes", ctypes.c_void_p), ("m", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64),
+        ("sessions", ctypes.c_void_p), ("sub_limit", ctypes.c_uint64), ("update_table", ctypes.c_uint64),
+        ("tables", ctypes.c_void_p), ("n_tables", ctypes.c_uint64),
+        ("ring", ctypes.c_void_p), ("heads", ctypes.c_void_p), ("c", ctypes.c_uint64), ("qc", ctypes.c_uint64),
+        ("now_ms", ctypes.c_uint64), ("deadlines", ctypes.c_void_p), ("ref_limit", ctypes.c_uint64), ("cap_out", ctypes.c_uint64),
+        ("out_offsets", ctypes.c_void_p), ("out_opts", ctypes.c_void_p), ("out_verdicts", ctypes.c_void_p),
+        ("out_pkt_ids", ctypes.c_void_p), ("out_refs", ctypes.c_void_p), ("out_class", ctypes.c_void_p),
+        ("out_status", ctypes.c_void_p), ("out_counts", ctypes.c_void_p),
+    ]
+
+
+class PmqueueStats(ctypes.Structure):
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("cap_in", ctypes.c_uint64), ("cap_boxes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("group", ctypes.c_uint64),
+        ("calls", ctypes.c_uint64), ("last_call_ms", ctypes.c_double),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = ctypes.sizeof(self)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
+
+
 class RelRunArgs(ctypes.Structure):
     """struct emqx_rel_run_args (include/emqx_rel.h): the buffers of one run call."""
     _fields_ = [
@@ -723,6 +774,19 @@ def lib():
         "emqx_mqueue_take_host": (i32, [vp, ctypes.POINTER(MqueueTakeArgs), vp]),
         "emqx_mqueue_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
         "emqx_mqueue_stats_get": (i32, [vp, ctypes.POINTER(MqueueStats)]),
+        "emqx_pmqueue_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
+        "emqx_pmqueue_destroy": (i32, [vp]),
+        "emqx_pmqueue_reserve": (i32, [vp, u64, u64]),
+        "emqx_pmqueue_put_batch": (i32, [vp, ctypes.POINTER(PmqueuePutArgs), vp]),
+        "emqx_pmqueue_take_batch": (i32, [vp, ctypes.POINTER(PmqueueTakeArgs), vp]),
+        "emqx_pmqueue_put_batch_device": (i32, [vp, ctypes.POINTER(PmqueuePutArgs), vp, vp]),
+        "emqx_pmqueue_put_batch_device_async": (i32, [vp, ctypes.POINTER(PmqueuePutArgs), vp, vp]),
+        "emqx_pmqueue_put_host": (i32, [vp, ctypes.POINTER(PmqueuePutArgs), vp]),
+        "emqx_pmqueue_take_batch_device": (i32, [vp, ctypes.POINTER(PmqueueTakeArgs), vp, vp]),
+        "emqx_pmqueue_take_batch_device_async": (i32, [vp, ctypes.POINTER(PmqueueTakeArgs), vp, vp]),
+        "emqx_pmqueue_take_host": (i32, [vp, ctypes.POINTER(PmqueueTakeArgs), vp]),
+        "emqx_pmqueue_set_tuning": (i32, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "emqx_pmqueue_stats_get": (i32, [vp, ctypes.POINTER(PmqueueStats)]),
         "emqx_rel_create": (i32, [ctypes.c_int32, ctypes.POINTER(vp)]),
         "emqx_rel_destroy": (i32, [vp]),
         "emqx_rel_reserve": (i32, [vp, u64, u64, u64]),

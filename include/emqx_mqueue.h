@@ -90,6 +90,8 @@
  *
  * Out of scope, kept by the caller: priority tables and shift_opts (such sessions are marked PASS),
  * awaiting_rel and the inbound QoS 2 path, log_dropped and the metrics, active_n, a NIF binding.
+ * The priority mqueue stage (emqx_pmqueue.h) serves sessions with a priority table in place of this
+ * one's two calls, so they need not be PASS.
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_ack.h: the calls
  * on one handle share its device scratch and are ordered by the handle.

@@ -73,7 +73,9 @@
  * active_n slicing of an inbox, which ids are still inflight (only the count is modelled;
  * emqx_ack.h keeps the ids and takes the acks, emqx_retry.h their ages), the id-to-pid lookup and
  * the send.  The queued messages themselves and the ack-driven dequeue/1 are the mqueue stage's
- * (emqx_mqueue.h): its put call runs behind this one and stores what the verdicts queue.
+ * (emqx_mqueue.h): its put call runs behind this one and stores what the verdicts queue.  A
+ * session with a priority table need not be PASS any more: with mq_max = 0 in its record this call
+ * marks its queue candidates EMQX_W_QUEUED and emqx_pmqueue.h applies the table behind it.
  *
  * Conventions as in emqx_match.h: int status, EMQX_* codes.  Threading as in emqx_inbox.h: the
  * calls on one handle share its device scratch and are ordered by the handle.
