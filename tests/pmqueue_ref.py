@@ -22,7 +22,10 @@ NO_REF, NO_CLASS = 0xFFFFFFFF, 0xFF
 (F_INPUT_REFUSED, F_BAD_SUB, F_OUTPUT_FULL, F_BAD_REF, F_BAD_HEAD, F_ROW_FULL, F_UNFIT, F_BAD_VERDICT, F_BAD_SRC,
  F_LIMITED) = 2, 4, 8, 0x10, 0x20, 0x40, 0x80, 0x100, 0x200, 0x400
 PRIO_INFINITY = 0x7FFFFFFF
-EVENTS = ("shifts", "unsorted_activations", "infinity_last", "evictions", "negative_credit_steps")
+EVENTS = ("shifts", "unsorted_activations", "infinity_last", "evictions", "negative_credit_steps",
+          # what the calls count on top of the model (the ring positions are the tables', the model has none)
+          "evictions_across_ring_end", "len_above_max_puts", "row_full_inboxes", "expired_at_16_up", "qos0_at_16_up",
+          "credit_zero_on_last_send")
 
 
 def term_key(key):
@@ -264,7 +267,8 @@ def put_reference(case, events=None, models=None):
     """One put call over the model: the outputs, and per OK session the model after it."""
     c, qc = case.ring.shape[1:]
     total = int(case.offsets[-1])
-    out = dict(verdicts=[0] * total, classes=[NO_CLASS] * total, evicted=[[NO_REF, 0]] * total, counts=[], models={})
+    out = dict(verdicts=[0] * total, classes=[NO_CLASS] * total, evicted=[[NO_REF, 0]] * total, counts=[], models={},
+               left_out=[])  # (for a test's ledger: the candidates a full ring had no place for)
     flags = 0
     sums = [0, 0, 0, 0, 0]
     for k, sub in enumerate(int(s) for s in case.subs):
@@ -282,6 +286,8 @@ def put_reference(case, events=None, models=None):
         flags |= F_LIMITED if int(case.sessions["mq_max"][sub]) else 0
         dropped0, evicted, qdropped, unstored = int(case.sessions["dropped"][sub]), 0, 0, 0
         alive = set()
+        at = list(read_head(case.heads[sub], t, qc)[0])  # counting only: the ring position of every class's oldest entry
+        above = set()
         for d in range(lo, hi):
             v = int(case.verdicts[d])
             if (v & W_MASK) == W_QUEUED_DROPPED or v & W_EVICTS:
@@ -297,9 +303,13 @@ def put_reference(case, events=None, models=None):
                 cl = cl if cl < len(prios) else int(t["default_class"])
             out["classes"][d] = cl
             out["verdicts"][d] = W_QUEUED
+            if mq.plen(prios[cl]) > mq.max_len and cl not in above and events is not None:
+                above.add(cl)
+                events["len_above_max_puts"] += 1
             if mq.plen(prios[cl]) >= qc and mq.plen(prios[cl]) != mq.max_len:  # a full ring beyond max_len: the stage's own limit
                 unstored += 1
                 flags |= F_ROW_FULL
+                out["left_out"].append(d)
                 continue
             ref = int(case.refs[d]) if case.refs is not None else d
             gone = mq_in((ref, int(case.opts[d]), d), prios[cl], mq)
@@ -309,10 +319,15 @@ def put_reference(case, events=None, models=None):
                 if gone[2] is None:
                     out["evicted"][d] = [gone[0], gone[1]]
                     evicted += 1
+                    at[cl] += 1
+                    if at[cl] > qc and events is not None:  # an old entry behind the ring end, after ones in front of it
+                        events["evictions_across_ring_end"] += 1
                 else:
                     out["verdicts"][gone[2]] = W_QUEUED_DROPPED | (out["verdicts"][gone[2]] & W_EVICTS)
                     alive.discard(gone[2])
                     qdropped += 1
+        if unstored and events is not None:
+            events["row_full_inboxes"] += 1
         after = dropped0 + evicted + qdropped
         out["counts"].append([len(alive), evicted, qdropped, unstored, mq.len, after & 0xFFFFFFFF, after >> 32, A_OK])
         out["models"][sub] = (mq, t, after)
@@ -355,10 +370,16 @@ def take_reference(case, cap_out=None, events=None, models=None):
                 return False
             return case.now > int(case.deadlines[msg[0]])
 
-        items = dequeue(batch_n(int(rec["inflight_max"]), int(rec["inflight"])), mq, is_expired)
+        budget = batch_n(int(rec["inflight_max"]), int(rec["inflight"]))
+        items = dequeue(budget, mq, is_expired)
         pkt = int(rec["next_pkt_id"])
         cnt = [0, 0, 0, mq.len]
+        at = list(read_head(case.heads[sub], t, qc)[0])  # counting only
         for msg, p, expired in items:
+            pos, at[prios.index(p)] = at[prios.index(p)] % qc, at[prios.index(p)] + 1
+            if events is not None and pos >= 16:
+                events["expired_at_16_up"] += expired
+                events["qos0_at_16_up"] += not expired and msg[1] & 3 == 0
             out["refs"].append(msg[0])
             out["opts"].append(msg[1])
             out["classes"].append(prios.index(p))
@@ -375,6 +396,8 @@ def take_reference(case, cap_out=None, events=None, models=None):
                 out["pkt_ids"].append(pkt)
                 pkt = 1 if pkt == 65535 else pkt + 1
                 cnt[0] += 1
+        if events is not None and budget and cnt[0] == budget and mq.last_prio is not None and mq.p_credit == 0:
+            events["credit_zero_on_last_send"] += 1
         out["counts"].append(cnt)
         out["offsets"].append(len(out["refs"]))
         out["models"][sub] = (mq, t, dict(next_pkt_id=pkt, inflight=min(int(rec["inflight"]) + cnt[0], 0xFFFFFFFF)))

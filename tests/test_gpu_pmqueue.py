@@ -2,7 +2,8 @@
 through emqx_pmqueue_*_batch, _batch_device and _batch_device_async, exact against the literal restatement and
 byte for byte what the host evaluator leaves (outputs, rings, heads, records), with sentinels behind
 every output; on a default handle and on one whose single block strides and whose scan carries at every
-total; every group width; the count read on the device; the cycle window -> record -> stamp -> put -> ack run -> stamp
+total; every group width; the lattice of tests/pmqueue_cases.py (C x Qc x group width) from uploaded tables and with the tables
+kept on the device; the count read on the device; the cycle window -> record -> stamp -> put -> ack run -> stamp
 -> take -> record -> stamp on one stream with no host read, against the restatements of all four stages."""
 
 import os
@@ -280,9 +281,11 @@ def test_every_group_width_gives_the_same_bytes(T, group):
     h = T.Pmqueue(0)
     h.set_tuning("group", group)
     assert h.stats()["group"] == group
-    for name in ("many_inboxes", "inbox_2349", "inbox_1024", "c8_q64_full_e6", "row_full", "unfit_tables"):
+    for name in ("many_inboxes", "inbox_2349", "inbox_1024", "c8_q64_full_e6", "row_full", "unfit_tables", "q128_full_bytes",
+                 "one_group_last_tile"):
         check_put_everywhere(T, h, next(c for c in PUT_CASES if c.name == name))
-    for name in ("many_sessions", "full_row_budget_1000", "full_row_budget_4", "expired_and_qos0", "statuses", "subs_null"):
+    for name in ("many_sessions", "full_row_budget_1000", "full_row_budget_4", "expired_and_qos0", "statuses", "subs_null",
+                 "q128_full_bytes", "q32_bits_word1", "one_group_last_tile"):
         check_take_everywhere(T, h, next(c for c in TAKE_CASES if c.name == name))
 
 
@@ -319,6 +322,99 @@ def test_async_needs_the_scratch_reserved(T):
     import torch
     torch.cuda.synchronize()
     assert b.outputs(T).summary["sessions"] == b.m and h.stats()["calls"] == 1 and h.stats()["cap_boxes"] == b.cap_boxes
+
+
+# ---- the lattice: C x Qc x group width ------------------------------------------------------------
+
+def run_lattice(T, h, c, qc, g):
+    """The rounds of tests/pmqueue_cases.py's lattice at one shape, sized around the group width g: every
+    call through all three device forms against the restatement and the host's bytes; the host's tables
+    carry the world on."""
+    from tests.test_pmqueue_cpu import put, take
+    lat = C.Lattice(c, qc)
+    for kind, case in lat.rounds(g):
+        if kind == "put":
+            check_put_everywhere(T, h, case)
+            lat.advance(kind, case, *put(T, case)[1:])
+            continue
+        for cap in ("case", case.room)[case.cap_out == case.room:]:  # the short round is repeated with room
+            check_take_everywhere(T, h, case, cap_out=cap)
+            lat.advance(kind, case, *take(T, case, True, cap)[1:], cap)
+    assert lat.flags["take"] & R.F_OUTPUT_FULL and lat.events["evictions"] > 0
+    return lat
+
+
+@pytest.mark.parametrize("group", [4, 16, 64])
+@pytest.mark.parametrize("c,qc", C.LATTICE_SHAPES, ids=["c%d_q%d" % s for s in C.LATTICE_SHAPES])
+def test_lattice(T, c, qc, group):
+    """129 sessions (a last tile of one group at every width), inboxes of 0, 1, G - 1, G, G + 1, 2 G + 1 and
+    3 Qc deliveries, tables of fewer classes than rings, max_len up to Qc, mult with base, heads at Qc - 1,
+    expired and QoS 0 entries in every ring word."""
+    h = T.Pmqueue(0)
+    h.set_tuning("group", group)
+    run_lattice(T, h, c, qc, group)
+
+
+@pytest.mark.parametrize("group", [8, 32])
+@pytest.mark.parametrize("c,qc", [(1, 128), (8, 128), (5, 8)], ids=["c1_q128", "c8_q128", "c5_q8"])
+def test_lattice_one_block_scan_chunk_1(T, c, qc, group):
+    """One block strides every tile, the take's scan carries at every total."""
+    h = T.Pmqueue(0)
+    for key, value in (("max_blocks", 1), ("scan_chunk", 1), ("group", group)):
+        h.set_tuning(key, value)
+    run_lattice(T, h, c, qc, group)
+
+
+def test_lattice_state_stays_on_the_device(T):
+    """C 8, Qc 128, G 4: the six rounds (and the repeat of the short take) are enqueued on one stream; records,
+    rings and heads are uploaded once and never read or written by the host in between, only the inflight
+    column is stored from the host before a take (the acks).  Outputs and a device-to-device copy of the
+    tables are kept per call and read at the end: a head or a ring entry the device writes in a form its
+    own next call reads differently shows here, and not where every call starts from uploaded tables."""
+    import torch
+    from tests.test_pmqueue_cpu import put, take
+    c, qc, g = 8, 128, 4
+    lat = C.Lattice(c, qc)
+    w, n = lat.world, lat.n
+    d_tables = dev_raw(w.tables)
+    d_sessions, d_ring, d_heads = (dev_raw(x, GUARD) for x in (w.sessions, w.ring, w.heads))
+    d_inflight = d_sessions[:n * 4].view(torch.int32).view(n, 8)[:, 0]
+    h = T.Pmqueue(0)
+    h.set_tuning("group", g)
+    h.reserve(C.REF_BASE, n + 1)
+    stream = torch.cuda.Stream(device=DEV)
+    calls = []
+    for kind, case in lat.rounds(g):
+        for cap in ("case",) if kind == "put" else ("case", case.room)[case.cap_out == case.room:]:
+            b = PutBatch(T, case) if kind == "put" else TakeBatch(T, case, cap_out=cap)
+            for name, t in (("tables", d_tables), ("sessions", d_sessions), ("ring", d_ring), ("heads", d_heads)):
+                setattr(b.args, name, t.data_ptr())
+            inflight = dev(case.sessions["inflight"], np.uint32)
+            stream.wait_stream(torch.cuda.current_stream())  # the inputs were filled there
+            with torch.cuda.stream(stream):
+                if kind == "put":
+                    h.put_device_async(b.args, b.summary.data_ptr(), stream=stream.cuda_stream)
+                else:
+                    d_inflight.copy_(inflight)
+                    h.take_device_async(b.args, b.summary.data_ptr(), stream=stream.cuda_stream)
+                after = [x.clone() for x in (d_sessions, d_ring, d_heads)]  # device to device, on the stream
+            want = put(T, case) if kind == "put" else take(T, case, True, cap)
+            calls.append((kind, case, cap, b, inflight, after, want))
+            lat.advance(kind, case, *want[1:], *(() if kind == "put" else (cap,)))
+    stream.synchronize()
+    # ---- only now the host reads
+    fulls = 0
+    for kind, case, cap, b, _, after, (want, sessions, ring, heads) in calls:
+        got = b.outputs(T)
+        d_s, d_r, d_h = back(after[0], w.sessions, "the records"), back(after[1], w.ring, "the rings"), back(after[2], w.heads, "the heads")
+        if kind == "put":
+            C.check_put(case.reference(), got, case, d_s, d_r, d_h)
+        else:
+            C.check_take(case.reference(cap), got, case, d_s, d_r, d_h)
+            fulls += bool(got.summary["flags"] & R.F_OUTPUT_FULL)
+        same(got, want)
+        assert d_s.tobytes() == sessions.tobytes() and d_r.tobytes() == ring.tobytes() and d_h.tobytes() == heads.tobytes(), case.name
+    assert len(calls) == 7 and fulls == 1
 
 
 # ---- the cycle ----------------------------------------------------------------------------------

@@ -151,6 +151,24 @@ def test_put_cases_reach_what_they_name():
     assert by["infinity_head_held"]["models"][0][0].priorities() == [R.INF, 2, 0]
     assert by["infinity_last"]["models"][0][0].priorities() == [R.INF, 2, 0]
     assert by["many_inboxes"]["summary"][7] == 300 and by["many_inboxes"]["summary"][4] > 50
+    # the cases at the top of the byte fields, below C classes and at a one-group tile
+    case = next(c for c in PUT_CASES if c.name == "q128_full_bytes")
+    assert case.ring.shape[1:] == (8, 128) and (case.heads["len"] == 128).all() and sorted(case.heads["head"][0].tolist()) == sorted(C.Q128_HEADS)
+    assert [c[:6] for c in by["q128_full_bytes"]["counts"]] == [[8 * e - q, 8 * e - q, q, 0, 1024, 8 * e] for e, q in ((1, 0), (2, 0), (130, 16))]
+    ev = R.all_events()
+    R.put_reference(case, ev)
+    assert ev["evictions"] == 8 * 133 and ev["evictions_across_ring_end"] >= 1024 - sum(128 - h for h in C.Q128_HEADS)
+    ev = R.all_events()
+    R.put_reference(next(c for c in PUT_CASES if c.name == "q128_above_max"), ev)
+    assert by["q128_above_max"]["summary"][0] == R.F_ROW_FULL and by["q128_above_max"]["summary"][3:7] == [6, 0, 0, 4]
+    assert ev["len_above_max_puts"] == 3 and ev["row_full_inboxes"] == 1 and ev["evictions"] == 0
+    assert by["q128_above_max"]["models"][1][0].plen(5) == 106 and by["q128_above_max"]["models"][1][0].plen(2) == 128
+    case = next(c for c in PUT_CASES if c.name == "classes_below_c")
+    assert case.ring.shape[1] == 7 and int(case.tables["n_classes"][0]) == 3 and int(case.heads["len"][1][5]) == 3
+    assert by["classes_below_c"]["summary"][0] == R.F_BAD_HEAD and by["classes_below_c"]["classes"][:6] == [2, 0, 1, 2, 2, 2]
+    assert len(by["classes_below_c"]["models"][1][0].q) == 3 and by["classes_below_c"]["counts"][0] == by["classes_below_c"]["counts"][1]
+    ref = by["one_group_last_tile"]
+    assert len(ref["counts"]) == 65 and 65 % (256 // 4) == 1 and ref["counts"][64][7] == R.A_OK and ref["counts"][64][:3] == [6, 6, 5]
 
 
 @pytest.mark.parametrize("update_table", [True, False])
@@ -176,6 +194,33 @@ def test_take_cases_reach_what_they_name():
     for name in ("credit_negative", "negative_priority_reached", "credit_zero_at_entry", "full_row_budget_1000"):
         R.take_reference(next(c for c in TAKE_CASES if c.name == name), events=ev)
     assert ev["negative_credit_steps"] >= 3 and ev["shifts"] >= 2
+    # the cases at the top of the byte fields, in the second LDS word, below C classes and at a one-group tile
+    case = next(c for c in TAKE_CASES if c.name == "q128_full_bytes")
+    assert by["q128_full_bytes"]["counts"] == [[542, 277, 205, 0]] and by["q128_full_bytes"]["summary"][3] == 1024
+    two = (case.now > case.deadlines[case.ring["ref"][0]]) | ((case.ring["opts"][0] & 3) == 0)  # [8, 128] by ring position
+    assert two.reshape(8, 8, 16).any(axis=2).all(), "every one of the 64 words holds a bit"
+    case = next(c for c in TAKE_CASES if c.name == "q32_bits_word1")
+    row, live = case.ring[0, 0], [(15 + i) % 32 for i in range(20)]
+    marked = [p for p in live if case.now > int(case.deadlines[int(row["ref"][p])]) or int(row["opts"][p]) & 3 == 0]
+    assert marked and all(p >= 16 or p <= 2 for p in marked) and {p >> 4 for p in live} == {0, 1} and live[-1] == 2
+    ev = R.all_events()
+    R.take_reference(case, events=ev)
+    ref = by["q32_bits_word1"]
+    assert ref["counts"] == [[6, 1, 2, 15]] and ref["refs"] == [0, 1, 2, 3, 4, 5, 40, 6, 7] and 15 + ref["refs"][-1] == 22
+    assert ev["expired_at_16_up"] == 2 and ev["qos0_at_16_up"] == 1
+    ref = by["classes_below_c"]
+    assert ref["summary"][0] == R.F_BAD_HEAD and ref["counts"] == [[7, 0, 0, 0]] * 2 and set(ref["classes"]) == {0, 1, 2}
+    ref = by["one_group_last_tile"]
+    assert len(ref["status"]) == 65 and ref["status"][64] == R.A_OK and ref["counts"][64] == [5, 1, 0, 0]
+    first, again = (next(c for c in TAKE_CASES if c.name == n) for n in ("credit_ends_with_budget", "credit_ends_with_budget_again"))
+    ev = R.all_events()
+    R.take_reference(first, events=ev)
+    assert ev["credit_zero_on_last_send"] == 1 and ev["shifts"] == 0 and by["credit_ends_with_budget"]["counts"] == [[9, 0, 0, 5]]
+    mq, t, extra = by["credit_ends_with_budget"]["models"][0]
+    assert R.credits(0, mq) == 8 and mq.p_credit == 0 and extra["next_pkt_id"] == int(again.sessions["next_pkt_id"][0])
+    assert R.logical(mq, t) == R.logical(R.model_of(again.heads[0], t, again.ring[0], 16)[0], t)  # the second case starts there
+    R.take_reference(again, events=ev)
+    assert ev["shifts"] == 1 and by["credit_ends_with_budget_again"]["classes"] == [0, 0, 1, 1, 1]
 
 
 def test_take_output_full_then_repeated(T):
@@ -265,6 +310,77 @@ def test_fuzz_host_follows_the_restatement(T):
         for c in range(4):
             assert [r for r, k in came_out[sub] if k == c] == [r for r, k in put_in[sub] if k == c and r not in lost[sub]], (sub, c)
     assert int(w.sessions["mq_len"].sum()) == 0
+
+
+# ---- the lattice: C x Qc x group width ---------------------------------------------------------------
+
+LATTICE_REACHED = {}  # (c, qc) -> (the restatement's counters, the flags of put, the flags of take)
+# half of what the restatement counts over the eight shapes with the committed seed (the docstring below)
+LATTICE_FLOORS = dict(shifts=374, unsorted_activations=95, infinity_last=40, evictions=17860, evictions_across_ring_end=1781,
+                      negative_credit_steps=4871, len_above_max_puts=194, row_full_inboxes=109, expired_at_16_up=1492,
+                      qos0_at_16_up=971, credit_zero_on_last_send=17)
+PUT_FLAGS = R.F_BAD_SUB | R.F_BAD_HEAD | R.F_ROW_FULL | R.F_UNFIT | R.F_BAD_VERDICT | R.F_BAD_SRC | R.F_LIMITED
+TAKE_FLAGS = R.F_BAD_SUB | R.F_OUTPUT_FULL | R.F_BAD_REF | R.F_BAD_HEAD | R.F_UNFIT | R.F_LIMITED
+
+
+def run_lattice(T, c, qc, update_table=True, groups=(4, 16, 64)):
+    """The rounds of one shape through the host calls, every one checked against the restatement; the put
+    rounds are sized around the group widths in turn.  With ``update_table`` false every call runs twice:
+    once leaving heads and records alone, checked, and once more to carry the state on."""
+    lat = C.Lattice(c, qc)
+    for i, (kind, case) in enumerate(lat.rounds(groups)):
+        if kind == "put":
+            for update in (update_table, True)[update_table:]:
+                got, sessions, ring, heads = put(T, case, update)
+                C.check_put(case.reference(), got, case, sessions, ring, heads, update)
+            lat.advance(kind, case, sessions, ring, heads)
+            continue
+        for cap in ("case", case.room)[case.cap_out == case.room:]:  # the short round is repeated with room
+            for update in (update_table, True)[update_table:]:
+                got, sessions, ring, heads = take(T, case, update, cap)
+                C.check_take(case.reference(cap), got, case, sessions, ring, heads, update)
+            lat.advance(kind, case, sessions, ring, heads, cap)
+    # conservation: everything put and not evicted comes out once, FIFO within a class
+    w, h = lat.world, host(T)
+    w.sessions["inflight_max"] = 0
+    for _ in range(2):  # (a take hands out 1000 sends at the most, 8 rings of 128 hold 1024 entries)
+        lat.drained(h.take_host(None, w.tables, w.sessions, w.ring, w.heads, update_table=True))
+    lat.check_conservation()
+    return lat
+
+
+@pytest.mark.parametrize("update_table", [True, False])
+@pytest.mark.parametrize("c,qc", C.LATTICE_SHAPES, ids=["c%d_q%d" % s for s in C.LATTICE_SHAPES])
+def test_lattice_host_follows_the_restatement(T, c, qc, update_table):
+    lat = run_lattice(T, c, qc, update_table)
+    LATTICE_REACHED[(c, qc)] = (lat.events, lat.flags["put"], lat.flags["take"])
+
+
+def test_lattice_reaches_what_it_must(T):
+    """The restatement's own counters summed over the eight shapes (three put and three take rounds each,
+    129 sessions, seed C.LATTICE_SEED), as measured from the restatement on the CPU:
+
+        shifts 749, unsorted_activations 190, infinity_last 80, evictions 35720, evictions_across_ring_end 3562
+        (an old entry read behind the ring end after ones in front of it), negative_credit_steps 9743,
+        len_above_max_puts 389 (a class of an inbox that meets L > M), row_full_inboxes 219, expired_at_16_up 2984
+        and qos0_at_16_up 1943 (an item handed out from a ring position >= 16: an LDS word other than word 0),
+        credit_zero_on_last_send 34 (the budget's last send leaves credit 0).
+
+    Every floor is half of its count.  Every flag of either call but INPUT_REFUSED is raised somewhere."""
+    total, flags_put, flags_take = R.all_events(), 0, 0
+    for c, qc in C.LATTICE_SHAPES:
+        if (c, qc) not in LATTICE_REACHED:
+            lat = run_lattice(T, c, qc)
+            LATTICE_REACHED[(c, qc)] = (lat.events, lat.flags["put"], lat.flags["take"])
+        events, fp, ft = LATTICE_REACHED[(c, qc)]
+        for k, v in events.items():
+            total[k] += v
+        flags_put, flags_take = flags_put | fp, flags_take | ft
+    print("lattice events:", total)
+    assert set(LATTICE_FLOORS) == set(total)
+    for k, floor in LATTICE_FLOORS.items():
+        assert floor > 0 and total[k] >= floor, (k, total[k], floor)
+    assert flags_put == PUT_FLAGS and flags_take == TAKE_FLAGS, (hex(flags_put), hex(flags_take))
 
 
 # ---- the differential: one class of priority 0 is the plain mqueue -----------------------------------
