@@ -3,26 +3,22 @@
 // same code on both sides.  With EMQX_MQUEUE_NO_DEVICE this file compiles with a plain C++ compiler
 // into the host-only part (tests/c/test_mqueue_host.cpp): handles of device EMQX_MQUEUE_HOST_ONLY
 // alone.
-#ifndef EMQX_MQUEUE_NO_DEVICE
-#include <hip/hip_runtime.h>
+// The handle's shared fields, create and destroy, the ordering of its calls, the device call forms and
+// the staging are stage_host.h's; this file gives them its policy.
+#ifdef EMQX_MQUEUE_NO_DEVICE
+#define EMQX_STAGE_NO_DEVICE
 #endif
 
 #include <algorithm>
-#include <chrono>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
-#include <new>
 #include <utility>
 #include <vector>
 
 #include "../../include/emqx_mqueue.h"
 #include "mqueue.h"
-#ifndef EMQX_MQUEUE_NO_DEVICE
-#include "streams.h"
-#endif
+#include "stage_host.h"
 
 using namespace emqx;
 
@@ -46,30 +42,18 @@ static_assert(sizeof(emqx_mqueue_entry) == 8 && sizeof(emqx_mqueue_ring) == 8 &&
                   offsetof(emqx_window_session, next_pkt_id) == 4 * MQ_REC_NEXT_PKT && offsetof(emqx_window_session, flags) == 4 * AK_REC_FLAGS,
               "layout");
 
-struct emqx_mqueue {
-  int device = EMQX_MQUEUE_HOST_ONLY;
-  std::mutex mu;  // the calls of a handle, its scratch and its stats
+static_assert(EMQX_MQUEUE_HOST_ONLY == STAGE_HOST_ONLY, "host-only handles");
+
+struct emqx_mqueue : StageHandle {  // (stage_host.h)
   int64_t max_blocks = AK_MAX_BLOCKS, scan_chunk = AK_SCAN_BLOCK;
-  uint64_t calls = 0;
-  double last_call_ms = 0;
-  uint64_t cap_in = 0, cap_boxes = 0, scratch_bytes = 0;  // what the scratch takes
-#ifndef EMQX_MQUEUE_NO_DEVICE
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // behind the last call enqueued
-  bool inflight = false;
-  uint8_t* d_scratch = nullptr;
-  uint8_t* d_stage = nullptr;  // staging of the host entry points
-  uint64_t stage_cap = 0;
-#endif
+  uint64_t cap_in = 0, cap_boxes = 0;  // what the scratch takes
 };
 
 namespace {
 
-constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
+struct Policy;  // what the call forms of stage_host.h ask of this stage; with the device code below
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
+constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
 
 // What every form requires of its argument block, whichever memory it points into.
 bool batch_ok(const emqx_mqueue_put_args* b) {
@@ -118,57 +102,6 @@ bool refused(const emqx_mqueue_take_args* b, uint64_t m, uint64_t* sum) {
   if (m <= b->cap_boxes && m <= AK_MAX_TOTAL && (b->subs || m <= b->sub_limit)) return false;
   sum[MQ_S_FLAGS] = MQ_F_INPUT_REFUSED;
   return true;
-}
-
-void note_call(emqx_mqueue* h, double ms) {
-  ++h->calls;
-  if (ms >= 0) h->last_call_ms = ms;
-}
-
-int mqueue_create(int32_t device, emqx_mqueue** out) {
-  if (!out) return EMQX_EINVAL;
-  *out = nullptr;
-  if (device < -1 && device != EMQX_MQUEUE_HOST_ONLY) return EMQX_EINVAL;
-#ifdef EMQX_MQUEUE_NO_DEVICE
-  if (device >= -1) return EMQX_EDEVICE;
-#else
-  if (device == -1 && hipGetDevice(&device) != hipSuccess) return EMQX_EDEVICE;  // the current device
-  if (device >= 0) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return EMQX_EDEVICE;
-  }
-#endif
-  std::unique_ptr<emqx_mqueue> h(new (std::nothrow) emqx_mqueue());
-  if (!h) return EMQX_ENOMEM;
-  h->device = device;
-#ifndef EMQX_MQUEUE_NO_DEVICE
-  if (device >= 0) {
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
-      if (h->stream) (void)hipStreamDestroy(h->stream);
-      return EMQX_EDEVICE;
-    }
-  }
-#endif
-  *out = h.release();
-  return EMQX_OK;
-}
-
-int mqueue_destroy(emqx_mqueue* h) {
-  if (!h) return EMQX_EINVAL;
-#ifndef EMQX_MQUEUE_NO_DEVICE
-  if (h->device >= 0) {
-    (void)hipSetDevice(h->device);
-    if (h->inflight) (void)hipEventSynchronize(h->done);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->done) (void)hipEventDestroy(h->done);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-  }
-#endif
-  delete h;
-  return EMQX_OK;
 }
 
 // ---- the host evaluators -----------------------------------------------------------------------
@@ -338,31 +271,7 @@ int take_host(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary_
   return status_of(sum, summary_out);
 }
 
-#ifdef EMQX_MQUEUE_NO_DEVICE
-
-int mqueue_reserve(emqx_mqueue* h, uint64_t, uint64_t) { return h ? EMQX_EDEVICE : EMQX_EINVAL; }
-template <class B>
-int run_batch(emqx_mqueue* h, const B*, uint64_t*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-template <class B>
-int run_batch_device(emqx_mqueue* h, const B*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-template <class B>
-int run_batch_device_async(emqx_mqueue* h, const B*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-
-#else
-
-#define MQ_TRY(expr)                           \
-  do {                                         \
-    hipError_t _e = (expr);                    \
-    if (_e != hipSuccess) return EMQX_EDEVICE; \
-  } while (0)
-
-inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+#ifndef EMQX_MQUEUE_NO_DEVICE
 
 // What the scratch has to take for a call.
 struct Need {
@@ -397,45 +306,33 @@ Layout layout_of(uint64_t cap_in, uint64_t cap_boxes) {
   return l;
 }
 
-void drain(emqx_mqueue* h) {
-  if (h->inflight) (void)hipEventSynchronize(h->done);
-  h->inflight = false;
-}
-
 // Holds h->mu.  Grows the scratch.
 int reserve_locked(emqx_mqueue* h, uint64_t cap_in, uint64_t cap_boxes) {
-  const uint64_t in = std::max(cap_in, h->cap_in), boxes = std::max(cap_boxes, h->cap_boxes);
-  if (h->d_scratch && in == h->cap_in && boxes == h->cap_boxes) return EMQX_OK;
-  drain(h);
-  if (h->d_scratch) (void)hipFree(h->d_scratch);
-  h->d_scratch = nullptr;
-  h->cap_in = h->cap_boxes = h->scratch_bytes = 0;
-  const Layout l = layout_of(in, boxes);
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_scratch), l.bytes) != hipSuccess) return EMQX_ENOMEM;
+  uint64_t in = std::max(cap_in, h->cap_in), boxes = std::max(cap_boxes, h->cap_boxes);
+  const int rc = grow_scratch(h, layout_of(in, boxes).bytes);
+  if (rc != EMQX_OK) in = boxes = 0;  // there is no scratch any more
   h->cap_in = in;
   h->cap_boxes = boxes;
-  h->scratch_bytes = l.bytes;
-  return EMQX_OK;
+  return rc;
 }
 
 bool fits(emqx_mqueue* h, const Need& n) { return h->d_scratch && n.cap_in <= h->cap_in && n.cap_boxes <= h->cap_boxes; }
 
-bool al(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 // The device forms move ring pairs and counts 16 bytes at a time.
 bool aligned_ok(const emqx_mqueue_put_args* b) {
-  return al(b->inbox_subs, 3) && al(b->inbox_offsets, 7) && al(b->n_boxes, 7) && al(b->refs, 3) && al(b->sessions, 15) &&
-         al(b->ring, 15) && al(b->heads, 7) && al(b->out_evicted, 7) && al(b->out_unstored, 3);
+  return al(b->inbox_subs, 4) && al(b->inbox_offsets, 8) && al(b->n_boxes, 8) && al(b->refs, 4) && al(b->sessions, 16) &&
+         al(b->ring, 16) && al(b->heads, 8) && al(b->out_evicted, 8) && al(b->out_unstored, 4);
 }
 bool aligned_ok(const emqx_mqueue_take_args* b) {
-  return al(b->subs, 3) && al(b->n_boxes, 7) && al(b->sessions, 15) && al(b->ring, 15) && al(b->heads, 7) && al(b->deadlines, 7) &&
-         al(b->out_offsets, 7) && al(b->out_pkt_ids, 1) && al(b->out_refs, 3) && al(b->out_counts, 15);
+  return al(b->subs, 4) && al(b->n_boxes, 8) && al(b->sessions, 16) && al(b->ring, 16) && al(b->heads, 8) && al(b->deadlines, 8) &&
+         al(b->out_offsets, 8) && al(b->out_pkt_ids, 2) && al(b->out_refs, 4) && al(b->out_counts, 16);
 }
 
-int mqueue_reserve(emqx_mqueue* h, uint64_t cap_in, uint64_t cap_boxes) {
+int reserve(emqx_mqueue* h, uint64_t cap_in, uint64_t cap_boxes) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
   if (cap_in > AK_MAX_TOTAL || cap_boxes > AK_MAX_TOTAL) return EMQX_EINVAL;
-  MQ_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   std::lock_guard<std::mutex> g(h->mu);
   return reserve_locked(h, cap_in, cap_boxes);
 }
@@ -501,96 +398,35 @@ int launch(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint8_t* p, const Lay
   return mq_launch_take(a, s);
 }
 
-// Holds h->mu.  Orders the call behind the handle's previous one and enqueues the passes;
-// `summary` NULL: the handle's own summary words.
-template <class B>
-int enqueue(emqx_mqueue* h, const B* b, uint64_t* summary, hipStream_t s, uint64_t** d_sum_out) {
-  const Layout l = layout_of(h->cap_in, h->cap_boxes);
-  uint8_t* p = h->d_scratch;
-  uint64_t* d_sum = reinterpret_cast<uint64_t*>(p + l.ctr) + MQ_C_WORDS;
-  if (d_sum_out) *d_sum_out = d_sum;
-  if (h->inflight) MQ_TRY(hipStreamWaitEvent(s, h->done, 0));
-  const int rc = launch(h, b, p, l, summary ? summary : d_sum, s) == 0 ? EMQX_OK : EMQX_EDEVICE;
-  if (hipEventRecord(h->done, s) != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    h->inflight = false;
-    return EMQX_EDEVICE;
+struct Policy {
+  static constexpr size_t WORDS = MQ_S_WORDS;
+  template <class B>
+  static bool batch_ok(const B* b) {
+    return ::batch_ok(b);
   }
-  h->inflight = true;
-  return rc;
-}
-
-template <class B>
-int run_batch_device_async(emqx_mqueue* h, const B* b, uint64_t* summary, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!summary || !batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  MQ_TRY(hipSetDevice(h->device));
-  std::lock_guard<std::mutex> g(h->mu);
-  if (!fits(h, need_of(b))) return EMQX_EOVERFLOW;  // nothing is enqueued
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) MQ_TRY(after_null_stream(s));
-  const int rc = enqueue(h, b, summary, s, nullptr);
-  note_call(h, -1);
-  return rc;
-}
-
-// Holds h->mu.  The call on `s`, its summary read back, the stream synchronized.
-template <class B>
-int run_sync_locked(emqx_mqueue* h, const B* b, hipStream_t s, uint64_t* sum) {
-  uint64_t* d_sum = nullptr;
-  int rc = enqueue(h, b, nullptr, s, &d_sum);
-  if (rc == EMQX_OK && hipMemcpyAsync(sum, d_sum, MQ_S_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = EMQX_EDEVICE;
-  return rc;
-}
-
-template <class B>
-int run_batch_device(emqx_mqueue* h, const B* b, uint64_t* summary_out, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  MQ_TRY(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::lock_guard<std::mutex> g(h->mu);
-  const Need n = need_of(b);
-  if (!fits(h, n)) {
-    const int rc = reserve_locked(h, n.cap_in, n.cap_boxes);
-    if (rc != EMQX_OK) return rc;
+  template <class B>
+  static bool aligned_ok(const B* b) {
+    return ::aligned_ok(b);
   }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) MQ_TRY(after_null_stream(s));
-  uint64_t sum[MQ_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int rc = run_sync_locked(h, b, s, sum);
-  if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;
-  h->inflight = false;
-  if (rc != EMQX_OK) return rc;
-  note_call(h, ms_since(t0));
-  return status_of(sum, summary_out);
-}
-
-// Staging of the host entry points: sections of the handle's staging buffer, each 16-byte aligned.
-struct Stage {
-  uint64_t at = 0;
-  uint64_t place(uint64_t bytes) {
-    const uint64_t o = at;
-    at += (bytes + 15) & ~15ull;
-    return o;
+  template <class B>
+  static bool fits(emqx_mqueue* h, const B* b) {
+    return ::fits(h, need_of(b));
   }
+  template <class B>
+  static int reserve(emqx_mqueue* h, const B* b) {
+    const Need n = need_of(b);
+    return reserve_locked(h, n.cap_in, n.cap_boxes);
+  }
+  static Layout layout(const emqx_mqueue* h) { return layout_of(h->cap_in, h->cap_boxes); }
+  static uint64_t* own_summary(const emqx_mqueue* h, const Layout& l) {
+    return reinterpret_cast<uint64_t*>(h->d_scratch + l.ctr) + MQ_C_WORDS;
+  }
+  template <class B>
+  static int launch(emqx_mqueue* h, const B* b, uint8_t* p, const Layout& l, uint64_t* summary, hipStream_t s) {
+    return ::launch(h, b, p, l, summary, s);
+  }
+  static int status_of(const uint64_t* sum, uint64_t* summary_out) { return ::status_of(sum, summary_out); }
 };
-
-// Holds h->mu.
-int stage_reserve(emqx_mqueue* h, uint64_t bytes) {
-  const uint64_t need = std::max<uint64_t>(bytes, 16);
-  if (h->stage_cap >= need) return EMQX_OK;
-  drain(h);
-  if (h->d_stage) (void)hipFree(h->d_stage);
-  h->d_stage = nullptr;
-  h->stage_cap = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_stage), need + need / 2) != hipSuccess) return EMQX_ENOMEM;
-  h->stage_cap = need + need / 2;
-  return EMQX_OK;
-}
 
 // The rows the call names as tables of their own: session k reads row k; a subscriber the table
 // does not hold becomes id m, which that table does not hold either.
@@ -619,18 +455,6 @@ void gather_rows(uint64_t m, uint64_t q, uint64_t sub_limit, SubOf sub_of, const
   }
 }
 
-struct Copier {
-  uint8_t* D;
-  hipStream_t s;
-  bool ok = true;
-  void up(uint64_t o, const void* src, uint64_t bytes) {
-    if (ok && bytes) ok = hipMemcpyAsync(D + o, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-  }
-  void down(void* dst, uint64_t o, uint64_t bytes) {
-    if (ok && bytes) ok = hipMemcpyAsync(dst, D + o, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-  }
-};
-
 int run_batch(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_out) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
@@ -639,7 +463,7 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_o
   uint64_t sum[MQ_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t total;
   if (refused(b, m, &total, sum)) return status_of(sum, summary_out);
-  MQ_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   auto sub_of = [&](uint64_t k) -> uint64_t { return b->inbox_subs[k]; };
@@ -653,11 +477,11 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_o
     const int rc = reserve_locked(h, total, m);
     if (rc != EMQX_OK) return rc;
   }
-  Stage st;
+  Stage st{16};
   const uint64_t o_sub = st.place(ga.subs.size() * 4), o_off = st.place((m + 1) * 8), o_opt = st.place(total), o_ver = st.place(total),
                  o_ref = st.place(b->refs ? total * 4 : 0), o_tab = st.place(ga.recs.size() * 32), o_row = st.place(ga.rows.size() * 8),
                  o_hd = st.place(ga.heads.size() * 8), o_evi = st.place(total * 8), o_uns = st.place(std::max<uint64_t>(m, 1) * 4);
-  const int src = stage_reserve(h, st.at);
+  const int src = stage_reserve(h, st.at, 16);
   if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
@@ -671,10 +495,7 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_o
   d.heads = reinterpret_cast<emqx_mqueue_ring*>(D + o_hd);
   d.out_evicted = reinterpret_cast<emqx_mqueue_entry*>(D + o_evi);
   d.out_unstored = reinterpret_cast<uint32_t*>(D + o_uns);
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  Copier cp{D, s};
-  cp.ok = rc == EMQX_OK;
+  Copier cp = stage_copier(h);
   cp.up(o_sub, ga.subs.data(), m * 4);
   cp.up(o_off, b->inbox_offsets, (m + 1) * 8);
   cp.up(o_opt, b->box_opts, total);
@@ -683,8 +504,7 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_o
   if (b->sessions) cp.up(o_tab, ga.recs.data(), m * 32);
   cp.up(o_row, ga.rows.data(), m * q * 8);
   cp.up(o_hd, ga.heads.data(), m * 8);
-  if (!cp.ok) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = run_sync_locked(h, &d, s, sum);
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (rc == EMQX_OK) {
     cp.down(b->out_evicted, o_evi, total * 8);
     cp.down(b->out_unstored, o_uns, m * 4);
@@ -714,7 +534,7 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary_
   const uint64_t m = b->m, q = b->q;
   uint64_t sum[MQ_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (refused(b, m, sum)) return status_of(sum, summary_out);
-  MQ_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   auto sub_of = [&](uint64_t k) -> uint64_t { return b->subs ? b->subs[k] : k; };
@@ -729,11 +549,11 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary_
     if (rc != EMQX_OK) return rc;
   }
   const uint64_t cap = b->cap_out;
-  Stage st;
+  Stage st{16};
   const uint64_t o_sub = st.place(ga.subs.size() * 4), o_tab = st.place(ga.recs.size() * 32), o_row = st.place(ga.rows.size() * 8),
                  o_hd = st.place(ga.heads.size() * 8), o_ddl = st.place(n_dead * 8), o_off = st.place((m + 1) * 8), o_opt = st.place(cap),
                  o_ver = st.place(cap), o_pkt = st.place(cap * 2), o_ref = st.place(cap * 4), o_sta = st.place(m), o_cnt = st.place(m * 16);
-  const int src = stage_reserve(h, st.at);
+  const int src = stage_reserve(h, st.at, 16);
   if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
@@ -749,17 +569,13 @@ int run_batch(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary_
   d.out_refs = reinterpret_cast<uint32_t*>(D + o_ref);
   d.out_status = D + o_sta;
   d.out_counts = reinterpret_cast<uint32_t*>(D + o_cnt);
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  Copier cp{D, s};
-  cp.ok = rc == EMQX_OK;
+  Copier cp = stage_copier(h);
   cp.up(o_sub, ga.subs.data(), m * 4);
   cp.up(o_tab, ga.recs.data(), m * 32);
   cp.up(o_row, ga.rows.data(), m * q * 8);
   cp.up(o_hd, ga.heads.data(), m * 8);
   cp.up(o_ddl, b->deadlines, n_dead * 8);
-  if (!cp.ok) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = run_sync_locked(h, &d, s, sum);
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;  // the summary says what to bring back
   const bool full = (sum[MQ_S_FLAGS] & MQ_F_OUTPUT_FULL) != 0;
   const bool none = (sum[MQ_S_FLAGS] & MQ_F_INPUT_REFUSED) != 0;
@@ -827,9 +643,7 @@ int mqueue_stats_get(emqx_mqueue* h, emqx_mqueue_stats* out) {
   s.scratch_bytes = h->scratch_bytes;
   s.calls = h->calls;
   s.last_call_ms = h->last_call_ms;
-  const uint64_t nbytes = std::min<uint64_t>(out->size, sizeof(s));
-  s.size = nbytes;
-  std::memcpy(out, &s, nbytes);
+  stats_copy(out, s);
   return EMQX_OK;
 }
 
@@ -838,22 +652,22 @@ int mqueue_stats_get(emqx_mqueue* h, emqx_mqueue_stats* out) {
 extern "C" {
 
 int emqx_mqueue_create(int32_t device, emqx_mqueue** out) {
-  return guarded([&] { return mqueue_create(device, out); });
+  return guarded([&] { return stage_create(device, out); });
 }
 int emqx_mqueue_destroy(emqx_mqueue* h) {
-  return guarded([&] { return mqueue_destroy(h); });
+  return guarded([&] { return stage_destroy(h); });
 }
 int emqx_mqueue_reserve(emqx_mqueue* h, uint64_t cap_in, uint64_t cap_boxes) {
-  return guarded([&] { return mqueue_reserve(h, cap_in, cap_boxes); });
+  return guarded([&] { return reserve(h, cap_in, cap_boxes); });
 }
 int emqx_mqueue_put_batch(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_out) {
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_mqueue_put_batch_device(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_mqueue_put_batch_device_async(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_mqueue_put_host(emqx_mqueue* h, const emqx_mqueue_put_args* b, uint64_t* summary_out) {
   return guarded([&] { return put_host(h, b, summary_out); });
@@ -862,10 +676,10 @@ int emqx_mqueue_take_batch(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint6
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_mqueue_take_batch_device(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_mqueue_take_batch_device_async(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_mqueue_take_host(emqx_mqueue* h, const emqx_mqueue_take_args* b, uint64_t* summary_out) {
   return guarded([&] { return take_host(h, b, summary_out); });

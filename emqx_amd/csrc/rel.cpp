@@ -3,25 +3,21 @@
 // and the expiry predicate live in rel.h and are the same code on both sides.  With
 // EMQX_REL_NO_DEVICE this file compiles with a plain C++ compiler into the host-only part
 // (tests/c/test_rel_host.cpp): handles of device EMQX_REL_HOST_ONLY alone.
-#ifndef EMQX_REL_NO_DEVICE
-#include <hip/hip_runtime.h>
+// The handle's shared fields, create and destroy, the ordering of its calls, the device call forms and
+// the staging are stage_host.h's; this file gives them its policy.
+#ifdef EMQX_REL_NO_DEVICE
+#define EMQX_STAGE_NO_DEVICE
 #endif
 
 #include <algorithm>
-#include <chrono>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
-#include <new>
 #include <vector>
 
 #include "../../include/emqx_rel.h"
 #include "rel.h"
-#ifndef EMQX_REL_NO_DEVICE
-#include "streams.h"
-#endif
+#include "stage_host.h"
 
 using namespace emqx;
 
@@ -41,31 +37,19 @@ static_assert(RL_PRESENT == EMQX_WINDOW_PRESENT && RL_CONNECTED == EMQX_WINDOW_C
 static_assert(sizeof(emqx_window_session) == 4 * RL_REC_WORDS && offsetof(emqx_window_session, flags) == 4 * RL_REC_FLAGS, "layout");
 static_assert(rl_entry(5, 7) == EMQX_REL_ENTRY(5, 7), "entry");
 
-struct emqx_rel {
-  int device = EMQX_REL_HOST_ONLY;
-  std::mutex mu;  // the calls of a handle, its scratch and its stats
+static_assert(EMQX_REL_HOST_ONLY == STAGE_HOST_ONLY, "host-only handles");
+
+struct emqx_rel : StageHandle {  // (stage_host.h)
   int64_t lanes = 0;
   int64_t max_blocks = RL_MAX_BLOCKS, scan_chunk = RL_SCAN_BLOCK;
-  uint64_t calls = 0;
-  double last_call_ms = 0;
-  uint64_t cap_in = 0, cap_boxes = 0, w = 0, scratch_bytes = 0;  // what the scratch takes
-#ifndef EMQX_REL_NO_DEVICE
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // behind the last call enqueued
-  bool inflight = false;
-  uint8_t* d_scratch = nullptr;
-  uint8_t* d_stage = nullptr;  // staging of the host entry points
-  uint64_t stage_cap = 0;
-#endif
+  uint64_t cap_in = 0, cap_boxes = 0, w = 0;  // what the scratch takes
 };
 
 namespace {
 
-constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
+struct Policy;  // what the call forms of stage_host.h ask of this stage; with the device code below
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
+constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
 
 // What both calls share of their argument blocks; an expire call has no events (cap_in 0).
 struct Common {
@@ -98,14 +82,6 @@ bool batch_ok(const emqx_rel_expire_args* b) {
   return true;
 }
 
-// Host buffers only: offsets[0] = 0, no decrease.
-bool offsets_ok(const uint64_t* offsets, uint64_t m) {
-  if (offsets[0] != 0) return false;
-  for (uint64_t k = 0; k < m; ++k)
-    if (offsets[k + 1] < offsets[k]) return false;
-  return true;
-}
-
 // What the synchronous forms return for a finished call's summary.
 int status_of(const uint64_t* sum, uint64_t* summary_out) {
   if (summary_out) std::memcpy(summary_out, sum, RL_S_WORDS * sizeof(uint64_t));
@@ -120,57 +96,6 @@ bool refused(const Common& c, const uint64_t* offsets, uint64_t m, uint64_t* sum
   sum[RL_S_BOXES] = m;
   sum[RL_S_TOTAL] = boxes_ok && offsets ? offsets[m] : 0;
   return true;
-}
-
-void note_call(emqx_rel* h, double ms) {
-  ++h->calls;
-  if (ms >= 0) h->last_call_ms = ms;
-}
-
-int rel_create(int32_t device, emqx_rel** out) {
-  if (!out) return EMQX_EINVAL;
-  *out = nullptr;
-  if (device < -1 && device != EMQX_REL_HOST_ONLY) return EMQX_EINVAL;
-#ifdef EMQX_REL_NO_DEVICE
-  if (device >= -1) return EMQX_EDEVICE;
-#else
-  if (device == -1 && hipGetDevice(&device) != hipSuccess) return EMQX_EDEVICE;  // the current device
-  if (device >= 0) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return EMQX_EDEVICE;
-  }
-#endif
-  std::unique_ptr<emqx_rel> h(new (std::nothrow) emqx_rel());
-  if (!h) return EMQX_ENOMEM;
-  h->device = device;
-#ifndef EMQX_REL_NO_DEVICE
-  if (device >= 0) {
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
-      if (h->stream) (void)hipStreamDestroy(h->stream);
-      return EMQX_EDEVICE;
-    }
-  }
-#endif
-  *out = h.release();
-  return EMQX_OK;
-}
-
-int rel_destroy(emqx_rel* h) {
-  if (!h) return EMQX_EINVAL;
-#ifndef EMQX_REL_NO_DEVICE
-  if (h->device >= 0) {
-    (void)hipSetDevice(h->device);
-    if (h->inflight) (void)hipEventSynchronize(h->done);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->done) (void)hipEventDestroy(h->done);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-  }
-#endif
-  delete h;
-  return EMQX_OK;
 }
 
 // ---- the host evaluators -----------------------------------------------------------------------
@@ -285,31 +210,7 @@ int expire_host(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary_ou
   return status_of(sum, summary_out);
 }
 
-#ifdef EMQX_REL_NO_DEVICE
-
-int rel_reserve(emqx_rel* h, uint64_t, uint64_t, uint64_t) { return h ? EMQX_EDEVICE : EMQX_EINVAL; }
-template <class B>
-int run_batch(emqx_rel* h, const B*, uint64_t*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-template <class B>
-int run_batch_device(emqx_rel* h, const B*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-template <class B>
-int run_batch_device_async(emqx_rel* h, const B*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-
-#else
-
-#define RL_TRY(expr)                           \
-  do {                                         \
-    hipError_t _e = (expr);                    \
-    if (_e != hipSuccess) return EMQX_EDEVICE; \
-  } while (0)
-
-inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+#ifndef EMQX_REL_NO_DEVICE
 
 // The scratch: the tile totals of the route list, and the counters with the synchronous forms'
 // summary behind them.  The fold keeps a session's row in registers: no per-session scratch.
@@ -325,33 +226,19 @@ Layout layout_of(uint64_t cap_in) {
   return l;
 }
 
-void drain(emqx_rel* h) {
-  if (h->inflight) (void)hipEventSynchronize(h->done);
-  h->inflight = false;
-}
-
 // Holds h->mu.  Grows the scratch.
 int reserve_locked(emqx_rel* h, uint64_t cap_in, uint64_t cap_boxes, uint64_t w) {
-  const uint64_t cap = std::max(cap_in, h->cap_in), boxes = std::max(cap_boxes, h->cap_boxes), ww = std::max(w, h->w);
-  if (h->d_scratch && cap == h->cap_in && boxes == h->cap_boxes && ww == h->w) return EMQX_OK;
-  const Layout l = layout_of(cap);
-  if (!h->d_scratch || l.bytes != h->scratch_bytes) {
-    drain(h);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    h->d_scratch = nullptr;
-    h->cap_in = h->cap_boxes = h->w = h->scratch_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_scratch), l.bytes) != hipSuccess) return EMQX_ENOMEM;
-  }
+  uint64_t cap = std::max(cap_in, h->cap_in), boxes = std::max(cap_boxes, h->cap_boxes), ww = std::max(w, h->w);
+  const int rc = grow_scratch(h, layout_of(cap).bytes);
+  if (rc != EMQX_OK) cap = boxes = ww = 0;  // there is no scratch any more
   h->cap_in = cap;
   h->cap_boxes = boxes;
   h->w = ww;
-  h->scratch_bytes = l.bytes;
-  return EMQX_OK;
+  return rc;
 }
 
 bool fits(emqx_rel* h, const Common& c) { return h->d_scratch && c.cap_in <= h->cap_in && c.cap_boxes <= h->cap_boxes && c.w <= h->w; }
 
-bool al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 // The device forms move rows and counts 16 bytes at a time.
 bool aligned_ok(const emqx_rel_run_args* b) {
   return al(b->ev_subs, 4) && al(b->ev_offsets, 8) && al(b->n_boxes, 8) && al(b->events, 4) && al(b->ts, 8) && al(b->src, 4) &&
@@ -361,11 +248,11 @@ bool aligned_ok(const emqx_rel_expire_args* b) {
   return al(b->subs, 4) && al(b->n_boxes, 8) && al(b->sessions, 16) && al(b->rel, 16) && al(b->timeouts, 4) && al(b->out_counts, 16);
 }
 
-int rel_reserve(emqx_rel* h, uint64_t cap_in, uint64_t cap_boxes, uint64_t w) {
+int reserve(emqx_rel* h, uint64_t cap_in, uint64_t cap_boxes, uint64_t w) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
   if (cap_in > RL_MAX_TOTAL || cap_boxes > RL_MAX_TOTAL || !rl_w_ok(w)) return EMQX_EINVAL;
-  RL_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   std::lock_guard<std::mutex> g(h->mu);
   return reserve_locked(h, cap_in, cap_boxes, w);
 }
@@ -424,96 +311,35 @@ int launch(emqx_rel* h, const emqx_rel_expire_args* b, uint8_t* p, const Layout&
   return rl_launch_expire(a, s);
 }
 
-// Holds h->mu.  Orders the call behind the handle's previous one and enqueues the passes;
-// `summary` NULL: the handle's own summary words.
-template <class B>
-int enqueue(emqx_rel* h, const B* b, uint64_t* summary, hipStream_t s, uint64_t** d_sum_out) {
-  const Layout l = layout_of(h->cap_in);
-  uint8_t* p = h->d_scratch;
-  uint64_t* d_sum = reinterpret_cast<uint64_t*>(p + l.bytes - l.ctr) + RL_S_WORDS;
-  if (d_sum_out) *d_sum_out = d_sum;
-  if (h->inflight) RL_TRY(hipStreamWaitEvent(s, h->done, 0));
-  const int rc = launch(h, b, p, l, summary ? summary : d_sum, s) == 0 ? EMQX_OK : EMQX_EDEVICE;
-  if (hipEventRecord(h->done, s) != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    h->inflight = false;
-    return EMQX_EDEVICE;
+struct Policy {
+  static constexpr size_t WORDS = RL_S_WORDS;
+  template <class B>
+  static bool batch_ok(const B* b) {
+    return ::batch_ok(b);
   }
-  h->inflight = true;
-  return rc;
-}
-
-template <class B>
-int run_batch_device_async(emqx_rel* h, const B* b, uint64_t* summary, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!summary || !batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  RL_TRY(hipSetDevice(h->device));
-  std::lock_guard<std::mutex> g(h->mu);
-  if (!fits(h, common_of(b))) return EMQX_EOVERFLOW;  // nothing is enqueued
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) RL_TRY(after_null_stream(s));
-  const int rc = enqueue(h, b, summary, s, nullptr);
-  note_call(h, -1);
-  return rc;
-}
-
-// Holds h->mu.  The call on `s`, its summary read back, the stream synchronized.
-template <class B>
-int run_sync_locked(emqx_rel* h, const B* b, hipStream_t s, uint64_t* sum) {
-  uint64_t* d_sum = nullptr;
-  int rc = enqueue(h, b, nullptr, s, &d_sum);
-  if (rc == EMQX_OK && hipMemcpyAsync(sum, d_sum, RL_S_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = EMQX_EDEVICE;
-  return rc;
-}
-
-template <class B>
-int run_batch_device(emqx_rel* h, const B* b, uint64_t* summary_out, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  RL_TRY(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::lock_guard<std::mutex> g(h->mu);
-  const Common c = common_of(b);
-  if (!fits(h, c)) {
-    const int rc = reserve_locked(h, c.cap_in, c.cap_boxes, c.w);
-    if (rc != EMQX_OK) return rc;
+  template <class B>
+  static bool aligned_ok(const B* b) {
+    return ::aligned_ok(b);
   }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) RL_TRY(after_null_stream(s));
-  uint64_t sum[RL_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int rc = run_sync_locked(h, b, s, sum);
-  if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;
-  h->inflight = false;
-  if (rc != EMQX_OK) return rc;
-  note_call(h, ms_since(t0));
-  return status_of(sum, summary_out);
-}
-
-// Staging of the host entry points: sections of the handle's staging buffer, each 16-byte aligned.
-struct Stage {
-  uint64_t at = 0;
-  uint64_t place(uint64_t bytes) {
-    const uint64_t o = at;
-    at += (bytes + 15) & ~15ull;
-    return o;
+  template <class B>
+  static bool fits(emqx_rel* h, const B* b) {
+    return ::fits(h, common_of(b));
   }
+  template <class B>
+  static int reserve(emqx_rel* h, const B* b) {
+    const Common c = common_of(b);
+    return reserve_locked(h, c.cap_in, c.cap_boxes, c.w);
+  }
+  static Layout layout(const emqx_rel* h) { return layout_of(h->cap_in); }
+  static uint64_t* own_summary(const emqx_rel* h, const Layout& l) {
+    return reinterpret_cast<uint64_t*>(h->d_scratch + l.bytes - l.ctr) + RL_S_WORDS;
+  }
+  template <class B>
+  static int launch(emqx_rel* h, const B* b, uint8_t* p, const Layout& l, uint64_t* summary, hipStream_t s) {
+    return ::launch(h, b, p, l, summary, s);
+  }
+  static int status_of(const uint64_t* sum, uint64_t* summary_out) { return ::status_of(sum, summary_out); }
 };
-
-// Holds h->mu.
-int stage_reserve(emqx_rel* h, uint64_t bytes) {
-  const uint64_t need = std::max<uint64_t>(bytes, 16);
-  if (h->stage_cap >= need) return EMQX_OK;
-  drain(h);
-  if (h->d_stage) (void)hipFree(h->d_stage);
-  h->d_stage = nullptr;
-  h->stage_cap = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_stage), need + need / 2) != hipSuccess) return EMQX_ENOMEM;
-  h->stage_cap = need + need / 2;
-  return EMQX_OK;
-}
 
 // The rows, records and per-session limits the call names as tables of their own: session k reads
 // row k; a subscriber the table does not hold becomes id m, which that table does not hold either.
@@ -546,18 +372,6 @@ void scatter_rows(const uint32_t* subs, uint64_t m, uint64_t sub_limit, uint64_t
   }
 }
 
-struct Copier {
-  uint8_t* D;
-  hipStream_t s;
-  bool ok = true;
-  void up(uint64_t o, const void* src, uint64_t bytes) {
-    if (ok && bytes) ok = hipMemcpyAsync(D + o, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-  }
-  void down(void* dst, uint64_t o, uint64_t bytes) {
-    if (ok && bytes) ok = hipMemcpyAsync(dst, D + o, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-  }
-};
-
 int run_batch(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
@@ -567,7 +381,7 @@ int run_batch(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
   uint64_t sum[RL_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (refused(c, b->ev_offsets, m, sum)) return status_of(sum, summary_out);
   if (!offsets_ok(b->ev_offsets, m)) return EMQX_EINVAL;
-  RL_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   const uint64_t total = b->ev_offsets[m];
@@ -581,12 +395,12 @@ int run_batch(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
     const int rc = reserve_locked(h, total, m, b->w);
     if (rc != EMQX_OK) return rc;
   }
-  Stage st;
+  Stage st{16};
   const uint64_t o_sub = st.place(m * 4), o_off = st.place((m + 1) * 8), o_ev = st.place(total * 4), o_ts = st.place(total * 8),
                  o_src = st.place(total * 4), o_tab = st.place(ga.recs.size() * 32), o_row = st.place(ga.rows.size() * 8),
                  o_lim = st.place(m * 4), o_ver = st.place(total), o_rt = st.place(total * 4), o_cnt = st.place(m * 16),
                  o_arm = st.place(m);
-  const int src = stage_reserve(h, st.at);
+  const int src = stage_reserve(h, st.at, 16);
   if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
@@ -602,10 +416,7 @@ int run_batch(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
   d.out_route = reinterpret_cast<uint32_t*>(D + o_rt);
   d.out_counts = reinterpret_cast<uint32_t*>(D + o_cnt);
   d.out_arm = D + o_arm;
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  Copier cp{D, s};
-  cp.ok = rc == EMQX_OK;
+  Copier cp = stage_copier(h);
   cp.up(o_sub, ga.subs.data(), m * 4);
   cp.up(o_off, b->ev_offsets, (m + 1) * 8);
   cp.up(o_ev, b->events, total * 4);
@@ -614,8 +425,7 @@ int run_batch(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
   cp.up(o_tab, ga.recs.data(), m * 32);
   cp.up(o_row, ga.rows.data(), m * b->w * 8);
   if (b->maxes) cp.up(o_lim, ga.lims.data(), m * 4);
-  if (!cp.ok) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = run_sync_locked(h, &d, s, sum);
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (rc == EMQX_OK && hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;  // the summary says how much was routed
   if (rc == EMQX_OK) {
     cp.down(ga.rows.data(), o_row, m * b->w * 8);
@@ -641,7 +451,7 @@ int run_batch(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary_out)
   const uint64_t m = b->m;
   uint64_t sum[RL_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (refused(c, nullptr, m, sum)) return status_of(sum, summary_out);
-  RL_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   Gathered ga;
@@ -653,10 +463,10 @@ int run_batch(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary_out)
     const int rc = reserve_locked(h, 0, m, b->w);
     if (rc != EMQX_OK) return rc;
   }
-  Stage st;
+  Stage st{16};
   const uint64_t o_sub = st.place(m * 4), o_tab = st.place(ga.recs.size() * 32), o_row = st.place(ga.rows.size() * 8),
                  o_lim = st.place(m * 4), o_st = st.place(m), o_cnt = st.place(m * 16);
-  const int src = stage_reserve(h, st.at);
+  const int src = stage_reserve(h, st.at, 16);
   if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
@@ -666,16 +476,12 @@ int run_batch(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary_out)
   d.timeouts = b->timeouts ? reinterpret_cast<const uint32_t*>(D + o_lim) : nullptr;
   d.out_status = D + o_st;
   d.out_counts = reinterpret_cast<uint32_t*>(D + o_cnt);
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  Copier cp{D, s};
-  cp.ok = rc == EMQX_OK;
+  Copier cp = stage_copier(h);
   cp.up(o_sub, ga.subs.data(), m * 4);
   cp.up(o_tab, ga.recs.data(), m * 32);
   cp.up(o_row, ga.rows.data(), m * b->w * 8);
   if (b->timeouts) cp.up(o_lim, ga.lims.data(), m * 4);
-  if (!cp.ok) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = run_sync_locked(h, &d, s, sum);
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (rc == EMQX_OK) {
     cp.down(ga.rows.data(), o_row, m * b->w * 8);
     cp.down(b->out_status, o_st, m);
@@ -727,9 +533,7 @@ int rel_stats_get(emqx_rel* h, emqx_rel_stats* out) {
   s.lanes = static_cast<uint64_t>(h->lanes);
   s.calls = h->calls;
   s.last_call_ms = h->last_call_ms;
-  const uint64_t nbytes = std::min<uint64_t>(out->size, sizeof(s));
-  s.size = nbytes;
-  std::memcpy(out, &s, nbytes);
+  stats_copy(out, s);
   return EMQX_OK;
 }
 
@@ -738,22 +542,22 @@ int rel_stats_get(emqx_rel* h, emqx_rel_stats* out) {
 extern "C" {
 
 int emqx_rel_create(int32_t device, emqx_rel** out) {
-  return guarded([&] { return rel_create(device, out); });
+  return guarded([&] { return stage_create(device, out); });
 }
 int emqx_rel_destroy(emqx_rel* h) {
-  return guarded([&] { return rel_destroy(h); });
+  return guarded([&] { return stage_destroy(h); });
 }
 int emqx_rel_reserve(emqx_rel* h, uint64_t cap_in, uint64_t cap_boxes, uint64_t w) {
-  return guarded([&] { return rel_reserve(h, cap_in, cap_boxes, w); });
+  return guarded([&] { return reserve(h, cap_in, cap_boxes, w); });
 }
 int emqx_rel_run_batch(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_rel_run_batch_device(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_rel_run_batch_device_async(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_rel_run_host(emqx_rel* h, const emqx_rel_run_args* b, uint64_t* summary_out) {
   return guarded([&] { return run_host(h, b, summary_out); });
@@ -762,10 +566,10 @@ int emqx_rel_expire_batch(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* 
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_rel_expire_batch_device(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_rel_expire_batch_device_async(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_rel_expire_host(emqx_rel* h, const emqx_rel_expire_args* b, uint64_t* summary_out) {
   return guarded([&] { return expire_host(h, b, summary_out); });

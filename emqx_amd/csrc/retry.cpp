@@ -3,26 +3,22 @@
 // and is the same code on both sides.  With EMQX_RETRY_NO_DEVICE this file compiles with a plain
 // C++ compiler into the host-only part (tests/c/test_retry_host.cpp): handles of device
 // EMQX_RETRY_HOST_ONLY alone.
-#ifndef EMQX_RETRY_NO_DEVICE
-#include <hip/hip_runtime.h>
+// The handle's shared fields, create and destroy, the ordering of its calls, the device call forms and
+// the staging are stage_host.h's; this file gives them its policy.
+#ifdef EMQX_RETRY_NO_DEVICE
+#define EMQX_STAGE_NO_DEVICE
 #endif
 
 #include <algorithm>
-#include <chrono>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
-#include <new>
 #include <utility>
 #include <vector>
 
 #include "../../include/emqx_retry.h"
 #include "retry.h"
-#ifndef EMQX_RETRY_NO_DEVICE
-#include "streams.h"
-#endif
+#include "stage_host.h"
 
 using namespace emqx;
 
@@ -45,30 +41,18 @@ static_assert(sizeof(emqx_ack_slot) == 8 && sizeof(emqx_retry_item) == 8 && size
                   offsetof(emqx_window_session, inflight) == 4 * AK_REC_INFLIGHT && offsetof(emqx_window_session, flags) == 4 * AK_REC_FLAGS,
               "layout");
 
-struct emqx_retry {
-  int device = EMQX_RETRY_HOST_ONLY;
-  std::mutex mu;  // the calls of a handle, its scratch and its stats
+static_assert(EMQX_RETRY_HOST_ONLY == STAGE_HOST_ONLY, "host-only handles");
+
+struct emqx_retry : StageHandle {  // (stage_host.h)
   int64_t max_blocks = AK_MAX_BLOCKS, scan_chunk = AK_SCAN_BLOCK;
-  uint64_t calls = 0;
-  double last_call_ms = 0;
-  uint64_t cap_boxes = 0, w = 0, scratch_bytes = 0;  // what the scratch takes
-#ifndef EMQX_RETRY_NO_DEVICE
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // behind the last call enqueued
-  bool inflight = false;
-  uint8_t* d_scratch = nullptr;
-  uint8_t* d_stage = nullptr;  // staging of the host entry points
-  uint64_t stage_cap = 0;
-#endif
+  uint64_t cap_boxes = 0, w = 0;  // what the scratch takes
 };
 
 namespace {
 
-constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
+struct Policy;  // what the call forms of stage_host.h ask of this stage; with the device code below
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
+constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
 
 // What both calls share of their argument blocks.
 struct Common {
@@ -115,57 +99,6 @@ bool refused(const Common& c, uint64_t m, uint64_t* sum) {
   sum[RT_S_FLAGS] = RT_F_INPUT_REFUSED;
   sum[RT_S_BOXES] = m;
   return true;
-}
-
-void note_call(emqx_retry* h, double ms) {
-  ++h->calls;
-  if (ms >= 0) h->last_call_ms = ms;
-}
-
-int retry_create(int32_t device, emqx_retry** out) {
-  if (!out) return EMQX_EINVAL;
-  *out = nullptr;
-  if (device < -1 && device != EMQX_RETRY_HOST_ONLY) return EMQX_EINVAL;
-#ifdef EMQX_RETRY_NO_DEVICE
-  if (device >= -1) return EMQX_EDEVICE;
-#else
-  if (device == -1 && hipGetDevice(&device) != hipSuccess) return EMQX_EDEVICE;  // the current device
-  if (device >= 0) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return EMQX_EDEVICE;
-  }
-#endif
-  std::unique_ptr<emqx_retry> h(new (std::nothrow) emqx_retry());
-  if (!h) return EMQX_ENOMEM;
-  h->device = device;
-#ifndef EMQX_RETRY_NO_DEVICE
-  if (device >= 0) {
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
-      if (h->stream) (void)hipStreamDestroy(h->stream);
-      return EMQX_EDEVICE;
-    }
-  }
-#endif
-  *out = h.release();
-  return EMQX_OK;
-}
-
-int retry_destroy(emqx_retry* h) {
-  if (!h) return EMQX_EINVAL;
-#ifndef EMQX_RETRY_NO_DEVICE
-  if (h->device >= 0) {
-    (void)hipSetDevice(h->device);
-    if (h->inflight) (void)hipEventSynchronize(h->done);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->done) (void)hipEventDestroy(h->done);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-  }
-#endif
-  delete h;
-  return EMQX_OK;
 }
 
 // ---- the host evaluators -----------------------------------------------------------------------
@@ -298,31 +231,7 @@ int sweep_host(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary_
   return status_of(sum, summary_out);
 }
 
-#ifdef EMQX_RETRY_NO_DEVICE
-
-int retry_reserve(emqx_retry* h, uint64_t, uint64_t) { return h ? EMQX_EDEVICE : EMQX_EINVAL; }
-template <class B>
-int run_batch(emqx_retry* h, const B*, uint64_t*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-template <class B>
-int run_batch_device(emqx_retry* h, const B*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-template <class B>
-int run_batch_device_async(emqx_retry* h, const B*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-
-#else
-
-#define RT_TRY(expr)                           \
-  do {                                         \
-    hipError_t _e = (expr);                    \
-    if (_e != hipSuccess) return EMQX_EDEVICE; \
-  } while (0)
-
-inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+#ifndef EMQX_RETRY_NO_DEVICE
 
 // The scratch: the tile totals of a sweep; the counters with the scan's total and decision and the
 // synchronous forms' summary behind them.
@@ -338,42 +247,30 @@ Layout layout_of(uint64_t cap_boxes, uint64_t w) {
   return l;
 }
 
-void drain(emqx_retry* h) {
-  if (h->inflight) (void)hipEventSynchronize(h->done);
-  h->inflight = false;
-}
-
 // Holds h->mu.  Grows the scratch.
 int reserve_locked(emqx_retry* h, uint64_t cap_boxes, uint64_t w) {
-  const uint64_t boxes = std::max(cap_boxes, h->cap_boxes), ww = std::max(w, h->w);
-  if (h->d_scratch && boxes == h->cap_boxes && ww == h->w) return EMQX_OK;
-  drain(h);
-  if (h->d_scratch) (void)hipFree(h->d_scratch);
-  h->d_scratch = nullptr;
-  h->cap_boxes = h->w = h->scratch_bytes = 0;
-  const Layout l = layout_of(boxes, ww);
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_scratch), l.bytes) != hipSuccess) return EMQX_ENOMEM;
+  uint64_t boxes = std::max(cap_boxes, h->cap_boxes), ww = std::max(w, h->w);
+  const int rc = grow_scratch(h, layout_of(boxes, ww).bytes);
+  if (rc != EMQX_OK) boxes = ww = 0;  // there is no scratch any more
   h->cap_boxes = boxes;
   h->w = ww;
-  h->scratch_bytes = l.bytes;
-  return EMQX_OK;
+  return rc;
 }
 
 bool fits(emqx_retry* h, const Common& c) { return h->d_scratch && c.cap_boxes <= h->cap_boxes && c.w <= h->w; }
 
-bool al(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 // The device forms move rows, stamp rows and counts 16 bytes at a time.
-bool aligned_ok(const emqx_retry_stamp_args* b) { return al(b->subs, 3) && al(b->n_boxes, 7) && al(b->slots, 15) && al(b->stamps, 15); }
+bool aligned_ok(const emqx_retry_stamp_args* b) { return al(b->subs, 4) && al(b->n_boxes, 8) && al(b->slots, 16) && al(b->stamps, 16); }
 bool aligned_ok(const emqx_retry_sweep_args* b) {
-  return al(b->subs, 3) && al(b->n_boxes, 7) && al(b->slots, 15) && al(b->stamps, 15) && al(b->sessions, 15) && al(b->intervals, 3) &&
-         al(b->deadlines, 7) && al(b->out_offsets, 7) && al(b->out_items, 7) && al(b->out_counts, 15) && al(b->out_timers, 3);
+  return al(b->subs, 4) && al(b->n_boxes, 8) && al(b->slots, 16) && al(b->stamps, 16) && al(b->sessions, 16) && al(b->intervals, 4) &&
+         al(b->deadlines, 8) && al(b->out_offsets, 8) && al(b->out_items, 8) && al(b->out_counts, 16) && al(b->out_timers, 4);
 }
 
-int retry_reserve(emqx_retry* h, uint64_t cap_boxes, uint64_t w) {
+int reserve(emqx_retry* h, uint64_t cap_boxes, uint64_t w) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
   if (cap_boxes > AK_MAX_TOTAL || !ak_w_ok(w)) return EMQX_EINVAL;
-  RT_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   std::lock_guard<std::mutex> g(h->mu);
   return reserve_locked(h, cap_boxes, w);
 }
@@ -428,96 +325,34 @@ int launch(emqx_retry* h, const emqx_retry_sweep_args* b, uint8_t* p, const Layo
   return rt_launch_sweep(a, s);
 }
 
-// Holds h->mu.  Orders the call behind the handle's previous one and enqueues the passes;
-// `summary` NULL: the handle's own summary words.
-template <class B>
-int enqueue(emqx_retry* h, const B* b, uint64_t* summary, hipStream_t s, uint64_t** d_sum_out) {
-  const Layout l = layout_of(h->cap_boxes, h->w);
-  uint8_t* p = h->d_scratch;
-  uint64_t* d_sum = reinterpret_cast<uint64_t*>(p + l.tiles) + RT_C_WORDS;
-  if (d_sum_out) *d_sum_out = d_sum;
-  if (h->inflight) RT_TRY(hipStreamWaitEvent(s, h->done, 0));
-  const int rc = launch(h, b, p, l, summary ? summary : d_sum, s) == 0 ? EMQX_OK : EMQX_EDEVICE;
-  if (hipEventRecord(h->done, s) != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    h->inflight = false;
-    return EMQX_EDEVICE;
+struct Policy {
+  static constexpr size_t WORDS = RT_S_WORDS;
+  template <class B>
+  static bool batch_ok(const B* b) {
+    return ::batch_ok(b);
   }
-  h->inflight = true;
-  return rc;
-}
-
-template <class B>
-int run_batch_device_async(emqx_retry* h, const B* b, uint64_t* summary, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!summary || !batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  RT_TRY(hipSetDevice(h->device));
-  std::lock_guard<std::mutex> g(h->mu);
-  if (!fits(h, common_of(b))) return EMQX_EOVERFLOW;  // nothing is enqueued
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) RT_TRY(after_null_stream(s));
-  const int rc = enqueue(h, b, summary, s, nullptr);
-  note_call(h, -1);
-  return rc;
-}
-
-// Holds h->mu.  The call on `s`, its summary read back, the stream synchronized.
-template <class B>
-int run_sync_locked(emqx_retry* h, const B* b, hipStream_t s, uint64_t* sum) {
-  uint64_t* d_sum = nullptr;
-  int rc = enqueue(h, b, nullptr, s, &d_sum);
-  if (rc == EMQX_OK && hipMemcpyAsync(sum, d_sum, RT_S_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = EMQX_EDEVICE;
-  return rc;
-}
-
-template <class B>
-int run_batch_device(emqx_retry* h, const B* b, uint64_t* summary_out, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  RT_TRY(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::lock_guard<std::mutex> g(h->mu);
-  const Common c = common_of(b);
-  if (!fits(h, c)) {
-    const int rc = reserve_locked(h, c.cap_boxes, c.w);
-    if (rc != EMQX_OK) return rc;
+  template <class B>
+  static bool aligned_ok(const B* b) {
+    return ::aligned_ok(b);
   }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) RT_TRY(after_null_stream(s));
-  uint64_t sum[RT_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int rc = run_sync_locked(h, b, s, sum);
-  if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;
-  h->inflight = false;
-  if (rc != EMQX_OK) return rc;
-  note_call(h, ms_since(t0));
-  return status_of(sum, summary_out);
-}
-
-// Staging of the host entry points: sections of the handle's staging buffer, each 16-byte aligned.
-struct Stage {
-  uint64_t at = 0;
-  uint64_t place(uint64_t bytes) {
-    const uint64_t o = at;
-    at += (bytes + 15) & ~15ull;
-    return o;
+  template <class B>
+  static bool fits(emqx_retry* h, const B* b) {
+    return ::fits(h, common_of(b));
   }
+  template <class B>
+  static int reserve(emqx_retry* h, const B* b) {
+    return reserve_locked(h, b->cap_boxes, b->w);
+  }
+  static Layout layout(const emqx_retry* h) { return layout_of(h->cap_boxes, h->w); }
+  static uint64_t* own_summary(const emqx_retry* h, const Layout& l) {
+    return reinterpret_cast<uint64_t*>(h->d_scratch + l.tiles) + RT_C_WORDS;
+  }
+  template <class B>
+  static int launch(emqx_retry* h, const B* b, uint8_t* p, const Layout& l, uint64_t* summary, hipStream_t s) {
+    return ::launch(h, b, p, l, summary, s);
+  }
+  static int status_of(const uint64_t* sum, uint64_t* summary_out) { return ::status_of(sum, summary_out); }
 };
-
-// Holds h->mu.
-int stage_reserve(emqx_retry* h, uint64_t bytes) {
-  const uint64_t need = std::max<uint64_t>(bytes, 16);
-  if (h->stage_cap >= need) return EMQX_OK;
-  drain(h);
-  if (h->d_stage) (void)hipFree(h->d_stage);
-  h->d_stage = nullptr;
-  h->stage_cap = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_stage), need + need / 2) != hipSuccess) return EMQX_ENOMEM;
-  h->stage_cap = need + need / 2;
-  return EMQX_OK;
-}
 
 // The rows the call names as tables of their own: session k reads row k; a subscriber the table
 // does not hold becomes id m, which that table does not hold either.
@@ -549,18 +384,6 @@ void scatter_rows(const Common& c, uint64_t m, emqx_ack_slot* slots, uint64_t* s
   }
 }
 
-struct Copier {
-  uint8_t* D;
-  hipStream_t s;
-  bool ok = true;
-  void up(uint64_t o, const void* src, uint64_t bytes) {
-    if (ok && bytes) ok = hipMemcpyAsync(D + o, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-  }
-  void down(void* dst, uint64_t o, uint64_t bytes) {
-    if (ok && bytes) ok = hipMemcpyAsync(dst, D + o, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-  }
-};
-
 int run_batch(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary_out) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
@@ -569,7 +392,7 @@ int run_batch(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary_o
   const uint64_t m = b->m;
   uint64_t sum[RT_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (refused(c, m, sum)) return status_of(sum, summary_out);
-  RT_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   Gathered ga;
@@ -581,24 +404,20 @@ int run_batch(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary_o
     const int rc = reserve_locked(h, m, b->w);
     if (rc != EMQX_OK) return rc;
   }
-  Stage st;
+  Stage st{16};
   const uint64_t o_sub = st.place(ga.subs.size() * 4), o_row = st.place(ga.rows.size() * 8), o_stp = st.place(ga.stamps.size() * 8);
-  const int src = stage_reserve(h, st.at);
+  const int src = stage_reserve(h, st.at, 16);
   if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
   d.subs = reinterpret_cast<const uint32_t*>(D + o_sub);
   d.slots = reinterpret_cast<const emqx_ack_slot*>(D + o_row);
   d.stamps = reinterpret_cast<uint64_t*>(D + o_stp);
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  Copier cp{D, s};
-  cp.ok = rc == EMQX_OK;
+  Copier cp = stage_copier(h);
   cp.up(o_sub, ga.subs.data(), m * 4);
   cp.up(o_row, ga.rows.data(), m * b->w * 8);
   cp.up(o_stp, ga.stamps.data(), m * b->w * 8);
-  if (!cp.ok) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = run_sync_locked(h, &d, s, sum);
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (rc == EMQX_OK) {
     cp.down(ga.stamps.data(), o_stp, m * b->w * 8);
     if (!cp.ok) rc = EMQX_EDEVICE;
@@ -619,7 +438,7 @@ int run_batch(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary_o
   const uint64_t m = b->m;
   uint64_t sum[RT_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (refused(c, m, sum)) return status_of(sum, summary_out);
-  RT_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   const bool replay = b->mode == RT_MODE_REPLAY;
@@ -643,12 +462,12 @@ int run_batch(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary_o
     const int rc = reserve_locked(h, m, b->w);
     if (rc != EMQX_OK) return rc;
   }
-  Stage st;
+  Stage st{16};
   const uint64_t o_sub = st.place(ga.subs.size() * 4), o_tab = st.place(recs.size() * 32), o_row = st.place(ga.rows.size() * 8),
                  o_stp = st.place(ga.stamps.size() * 8), o_ivl = st.place(ivals.size() * 4), o_ddl = st.place(n_dead * 8),
                  o_off = st.place((m + 1) * 8), o_itm = st.place(b->cap_out * 8), o_sta = st.place(m), o_cnt = st.place(m * 16),
                  o_tmr = st.place(m * 4);
-  const int src = stage_reserve(h, st.at);
+  const int src = stage_reserve(h, st.at, 16);
   if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
@@ -663,18 +482,14 @@ int run_batch(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary_o
   d.out_status = D + o_sta;
   d.out_counts = reinterpret_cast<uint32_t*>(D + o_cnt);
   d.out_timers = reinterpret_cast<uint32_t*>(D + o_tmr);
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  Copier cp{D, s};
-  cp.ok = rc == EMQX_OK;
+  Copier cp = stage_copier(h);
   cp.up(o_sub, ga.subs.data(), m * 4);
   cp.up(o_tab, recs.data(), m * 32);
   cp.up(o_row, ga.rows.data(), m * b->w * 8);
   cp.up(o_stp, ga.stamps.data(), m * b->w * 8);
   if (b->intervals) cp.up(o_ivl, ivals.data(), m * 4);
   cp.up(o_ddl, b->deadlines, n_dead * 8);
-  if (!cp.ok) rc = EMQX_EDEVICE;
-  if (rc == EMQX_OK) rc = run_sync_locked(h, &d, s, sum);
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;  // the summary says what to bring back
   const bool full = (sum[RT_S_FLAGS] & RT_F_OUTPUT_FULL) != 0;
   const bool none = (sum[RT_S_FLAGS] & RT_F_INPUT_REFUSED) != 0;
@@ -737,9 +552,7 @@ int retry_stats_get(emqx_retry* h, emqx_retry_stats* out) {
   s.scratch_bytes = h->scratch_bytes;
   s.calls = h->calls;
   s.last_call_ms = h->last_call_ms;
-  const uint64_t nbytes = std::min<uint64_t>(out->size, sizeof(s));
-  s.size = nbytes;
-  std::memcpy(out, &s, nbytes);
+  stats_copy(out, s);
   return EMQX_OK;
 }
 
@@ -748,22 +561,22 @@ int retry_stats_get(emqx_retry* h, emqx_retry_stats* out) {
 extern "C" {
 
 int emqx_retry_create(int32_t device, emqx_retry** out) {
-  return guarded([&] { return retry_create(device, out); });
+  return guarded([&] { return stage_create(device, out); });
 }
 int emqx_retry_destroy(emqx_retry* h) {
-  return guarded([&] { return retry_destroy(h); });
+  return guarded([&] { return stage_destroy(h); });
 }
 int emqx_retry_reserve(emqx_retry* h, uint64_t cap_boxes, uint64_t w) {
-  return guarded([&] { return retry_reserve(h, cap_boxes, w); });
+  return guarded([&] { return reserve(h, cap_boxes, w); });
 }
 int emqx_retry_stamp_batch(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary_out) {
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_retry_stamp_batch_device(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_retry_stamp_batch_device_async(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_retry_stamp_host(emqx_retry* h, const emqx_retry_stamp_args* b, uint64_t* summary_out) {
   return guarded([&] { return stamp_host(h, b, summary_out); });
@@ -772,10 +585,10 @@ int emqx_retry_sweep_batch(emqx_retry* h, const emqx_retry_sweep_args* b, uint64
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_retry_sweep_batch_device(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_retry_sweep_batch_device_async(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_retry_sweep_host(emqx_retry* h, const emqx_retry_sweep_args* b, uint64_t* summary_out) {
   return guarded([&] { return sweep_host(h, b, summary_out); });

@@ -3,24 +3,20 @@
 // window.h and is the same code on both sides.  With EMQX_WINDOW_NO_DEVICE this file compiles with
 // a plain C++ compiler into the host-only part (tests/c/test_window_host.cpp): handles of device
 // EMQX_WINDOW_HOST_ONLY alone.
-#ifndef EMQX_WINDOW_NO_DEVICE
-#include <hip/hip_runtime.h>
+// The handle's shared fields, create and destroy, the ordering of its calls, the device call forms and
+// the staging are stage_host.h's; this file gives them its policy.
+#ifdef EMQX_WINDOW_NO_DEVICE
+#define EMQX_STAGE_NO_DEVICE
 #endif
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
-#include <new>
 #include <vector>
 
 #include "../../include/emqx_window.h"
 #include "window.h"
-#ifndef EMQX_WINDOW_NO_DEVICE
-#include "streams.h"
-#endif
+#include "stage_host.h"
 
 using namespace emqx;
 
@@ -38,31 +34,19 @@ static_assert(WN_PRESENT == EMQX_WINDOW_PRESENT && WN_CONNECTED == EMQX_WINDOW_C
                   WN_STORE_QOS0 == EMQX_WINDOW_STORE_QOS0 && WN_PASSF == EMQX_WINDOW_PASS,
               "record flags");
 
-struct emqx_window {
-  int device = EMQX_WINDOW_HOST_ONLY;
-  std::mutex mu;  // the calls of a handle, its scratch and its stats
+static_assert(EMQX_WINDOW_HOST_ONLY == STAGE_HOST_ONLY, "host-only handles");
+
+struct emqx_window : StageHandle {  // (stage_host.h)
   int64_t path = 0;
   int64_t max_blocks = WN_MAX_BLOCKS, scan_chunk = WN_SCAN_BLOCK;
-  uint64_t calls = 0;
-  double last_call_ms = 0;
-  uint64_t cap_in = 0, cap_boxes = 0, scratch_bytes = 0;  // what the scratch takes
-#ifndef EMQX_WINDOW_NO_DEVICE
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // behind the last call enqueued
-  bool inflight = false;
-  uint8_t* d_scratch = nullptr;
-  uint8_t* d_stage = nullptr;  // staging of the host entry point
-  uint64_t stage_cap = 0;
-#endif
+  uint64_t cap_in = 0, cap_boxes = 0;  // what the scratch takes
 };
 
 namespace {
 
-constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
+struct Policy;  // what the call forms of stage_host.h ask of this stage; with the device code below
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
+constexpr uint64_t MAX_SUB_LIMIT = 1ull << 32;
 
 // What every form requires of its argument block, whichever memory it points into.
 bool batch_ok(const emqx_window_batch* b) {
@@ -72,14 +56,6 @@ bool batch_ok(const emqx_window_batch* b) {
   if (b->cap_boxes && (!b->inbox_subs || !b->out_sessions || !b->out_counts)) return false;
   if (b->sub_limit && !b->sessions) return false;
   if (!b->n_boxes && b->m > b->cap_boxes) return false;
-  return true;
-}
-
-// Host buffers only: the inbox count, inbox_offsets[0] = 0, no decrease.
-bool offsets_ok(const emqx_window_batch* b, uint64_t m) {
-  if (b->inbox_offsets[0] != 0) return false;
-  for (uint64_t k = 0; k < m; ++k)
-    if (b->inbox_offsets[k + 1] < b->inbox_offsets[k]) return false;
   return true;
 }
 
@@ -99,65 +75,13 @@ bool refused(const emqx_window_batch* b, uint64_t m, uint64_t* sum) {
   return true;
 }
 
-void note_call(emqx_window* h, double ms) {
-  ++h->calls;
-  if (ms >= 0) h->last_call_ms = ms;
-}
-
-int window_create(int32_t device, emqx_window** out) {
-  if (!out) return EMQX_EINVAL;
-  *out = nullptr;
-  if (device < -1 && device != EMQX_WINDOW_HOST_ONLY) return EMQX_EINVAL;
-#ifdef EMQX_WINDOW_NO_DEVICE
-  if (device >= -1) return EMQX_EDEVICE;
-#else
-  if (device == -1 && hipGetDevice(&device) != hipSuccess) return EMQX_EDEVICE;  // the current device
-  if (device >= 0) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return EMQX_EDEVICE;
-  }
-#endif
-  std::unique_ptr<emqx_window> h(new (std::nothrow) emqx_window());
-  if (!h) return EMQX_ENOMEM;
-  h->device = device;
-#ifndef EMQX_WINDOW_NO_DEVICE
-  if (device >= 0) {
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
-      if (h->stream) (void)hipStreamDestroy(h->stream);
-      return EMQX_EDEVICE;
-    }
-  }
-#endif
-  *out = h.release();
-  return EMQX_OK;
-}
-
-int window_destroy(emqx_window* h) {
-  if (!h) return EMQX_EINVAL;
-#ifndef EMQX_WINDOW_NO_DEVICE
-  if (h->device >= 0) {
-    (void)hipSetDevice(h->device);
-    if (h->inflight) (void)hipEventSynchronize(h->done);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->done) (void)hipEventDestroy(h->done);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-  }
-#endif
-  delete h;
-  return EMQX_OK;
-}
-
 int run_host(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out) {
   if (!h || !batch_ok(b)) return EMQX_EINVAL;
   const auto t0 = std::chrono::steady_clock::now();
   const uint64_t m = b->n_boxes ? *b->n_boxes : b->m;
   uint64_t sum[WN_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (refused(b, m, sum)) return status_of(sum, summary_out);
-  if (!offsets_ok(b, m)) return EMQX_EINVAL;
+  if (!offsets_ok(b->inbox_offsets, m)) return EMQX_EINVAL;
   const uint64_t total = b->inbox_offsets[m];
   sum[WN_S_TOTAL] = total;
   sum[WN_S_BOXES] = m;
@@ -207,24 +131,7 @@ int run_host(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out) 
   return status_of(sum, summary_out);
 }
 
-#ifdef EMQX_WINDOW_NO_DEVICE
-
-int window_reserve(emqx_window* h, uint64_t, uint64_t) { return h ? EMQX_EDEVICE : EMQX_EINVAL; }
-int run_batch(emqx_window* h, const emqx_window_batch*, uint64_t*) { return h ? EMQX_EDEVICE : EMQX_EINVAL; }
-int run_batch_device(emqx_window* h, const emqx_window_batch*, uint64_t*, void*) { return h ? EMQX_EDEVICE : EMQX_EINVAL; }
-int run_batch_device_async(emqx_window* h, const emqx_window_batch*, uint64_t*, void*) {
-  return h ? EMQX_EDEVICE : EMQX_EINVAL;
-}
-
-#else
-
-#define WN_TRY(expr)                           \
-  do {                                         \
-    hipError_t _e = (expr);                    \
-    if (_e != hipSuccess) return EMQX_EDEVICE; \
-  } while (0)
-
-inline uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+#ifndef EMQX_WINDOW_NO_DEVICE
 
 // The scratch of a call: the tile totals, the prefix at every inbox head (and at the end), the
 // counters with the synchronous forms' summary behind them.
@@ -241,25 +148,14 @@ Layout layout_of(uint64_t cap_in, uint64_t cap_boxes) {
   return l;
 }
 
-void drain(emqx_window* h) {
-  if (h->inflight) (void)hipEventSynchronize(h->done);
-  h->inflight = false;
-}
-
 // Holds h->mu.  Grows the scratch to take cap_in deliveries and cap_boxes inboxes.
 int reserve_locked(emqx_window* h, uint64_t cap_in, uint64_t cap_boxes) {
-  const uint64_t cap = std::max(cap_in, h->cap_in), boxes = std::max(cap_boxes, h->cap_boxes);
-  if (h->d_scratch && cap == h->cap_in && boxes == h->cap_boxes) return EMQX_OK;
-  drain(h);
-  if (h->d_scratch) (void)hipFree(h->d_scratch);
-  h->d_scratch = nullptr;
-  h->cap_in = h->cap_boxes = h->scratch_bytes = 0;
-  const Layout l = layout_of(cap, boxes);
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_scratch), l.bytes) != hipSuccess) return EMQX_ENOMEM;
+  uint64_t cap = std::max(cap_in, h->cap_in), boxes = std::max(cap_boxes, h->cap_boxes);
+  const int rc = grow_scratch(h, layout_of(cap, boxes).bytes);
+  if (rc != EMQX_OK) cap = boxes = 0;  // there is no scratch any more
   h->cap_in = cap;
   h->cap_boxes = boxes;
-  h->scratch_bytes = l.bytes;
-  return EMQX_OK;
+  return rc;
 }
 
 bool fits(emqx_window* h, const emqx_window_batch* b) {
@@ -268,26 +164,21 @@ bool fits(emqx_window* h, const emqx_window_batch* b) {
 
 // The device forms move records and counts 16 bytes at a time.
 bool aligned_ok(const emqx_window_batch* b) {
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  return a16(b->sessions) && a16(b->out_sessions) && a16(b->out_counts) &&
-         (reinterpret_cast<uintptr_t>(b->inbox_offsets) & 7u) == 0 && (reinterpret_cast<uintptr_t>(b->n_boxes) & 7u) == 0 &&
-         (reinterpret_cast<uintptr_t>(b->inbox_subs) & 3u) == 0 && (reinterpret_cast<uintptr_t>(b->pkt_ids) & 1u) == 0;
+  return al(b->sessions, 16) && al(b->out_sessions, 16) && al(b->out_counts, 16) && al(b->inbox_offsets, 8) && al(b->n_boxes, 8) &&
+         al(b->inbox_subs, 4) && al(b->pkt_ids, 2);
 }
 
-int window_reserve(emqx_window* h, uint64_t cap_in, uint64_t cap_boxes) {
+int reserve(emqx_window* h, uint64_t cap_in, uint64_t cap_boxes) {
   if (!h) return EMQX_EINVAL;
   if (h->device < 0) return EMQX_EDEVICE;
   if (cap_in > WN_MAX_TOTAL || cap_boxes > WN_MAX_TOTAL) return EMQX_EINVAL;
-  WN_TRY(hipSetDevice(h->device));
+  STAGE_TRY(hipSetDevice(h->device));
   std::lock_guard<std::mutex> g(h->mu);
   return reserve_locked(h, cap_in, cap_boxes);
 }
 
-// Holds h->mu.  Orders the call behind the handle's previous one and enqueues the passes;
-// `summary` NULL: the handle's own summary words.
-int enqueue(emqx_window* h, const emqx_window_batch* b, uint64_t* summary, hipStream_t s, uint64_t** d_sum_out) {
-  const Layout l = layout_of(h->cap_in, h->cap_boxes);
-  uint8_t* p = h->d_scratch;
+// The passes of one call over the handle's scratch; `summary`: where the last of them writes.
+int launch(emqx_window* h, const emqx_window_batch* b, uint8_t* p, const Layout& l, uint64_t* summary, hipStream_t s) {
   WnArgs a{};
   a.inbox_subs = b->inbox_subs;
   a.inbox_offsets = b->inbox_offsets;
@@ -306,59 +197,27 @@ int enqueue(emqx_window* h, const emqx_window_batch* b, uint64_t* summary, hipSt
   a.tile_tot = reinterpret_cast<uint64_t*>(p);
   a.head_pre = reinterpret_cast<uint64_t*>(p + l.tiles);
   a.ctr = reinterpret_cast<unsigned long long*>(p + l.tiles + l.heads);
-  uint64_t* d_sum = reinterpret_cast<uint64_t*>(p + l.tiles + l.heads) + WN_S_WORDS;
-  a.summary = summary ? summary : d_sum;
+  a.summary = summary;
   a.max_blocks = static_cast<uint32_t>(h->max_blocks);
   a.scan_chunk = static_cast<uint32_t>(h->scan_chunk);
-  if (d_sum_out) *d_sum_out = d_sum;
-  if (h->inflight) WN_TRY(hipStreamWaitEvent(s, h->done, 0));
-  const int rc = wn_launch(a, static_cast<int>(h->path), s) == 0 ? EMQX_OK : EMQX_EDEVICE;
-  if (hipEventRecord(h->done, s) != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    h->inflight = false;
-    return EMQX_EDEVICE;
-  }
-  h->inflight = true;
-  return rc;
+  return wn_launch(a, static_cast<int>(h->path), s);
 }
 
-int run_batch_device_async(emqx_window* h, const emqx_window_batch* b, uint64_t* summary, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!summary || !batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  WN_TRY(hipSetDevice(h->device));
-  std::lock_guard<std::mutex> g(h->mu);
-  if (!fits(h, b)) return EMQX_EOVERFLOW;  // nothing is enqueued
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) WN_TRY(after_null_stream(s));
-  const int rc = enqueue(h, b, summary, s, nullptr);
-  note_call(h, -1);
-  return rc;
-}
-
-int run_batch_device(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out, void* stream) {
-  if (!h) return EMQX_EINVAL;
-  if (h->device < 0) return EMQX_EDEVICE;
-  if (!batch_ok(b) || !aligned_ok(b)) return EMQX_EINVAL;
-  WN_TRY(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::lock_guard<std::mutex> g(h->mu);
-  if (!fits(h, b)) {
-    const int rc = reserve_locked(h, b->cap_in, b->cap_boxes);
-    if (rc != EMQX_OK) return rc;
+struct Policy {
+  static constexpr size_t WORDS = WN_S_WORDS;
+  static bool batch_ok(const emqx_window_batch* b) { return ::batch_ok(b); }
+  static bool aligned_ok(const emqx_window_batch* b) { return ::aligned_ok(b); }
+  static bool fits(emqx_window* h, const emqx_window_batch* b) { return ::fits(h, b); }
+  static int reserve(emqx_window* h, const emqx_window_batch* b) { return reserve_locked(h, b->cap_in, b->cap_boxes); }
+  static Layout layout(const emqx_window* h) { return layout_of(h->cap_in, h->cap_boxes); }
+  static uint64_t* own_summary(const emqx_window* h, const Layout& l) {
+    return reinterpret_cast<uint64_t*>(h->d_scratch + l.tiles + l.heads) + WN_S_WORDS;
   }
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  if (!stream) WN_TRY(after_null_stream(s));
-  uint64_t* d_sum = nullptr;
-  uint64_t sum[WN_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int rc = enqueue(h, b, nullptr, s, &d_sum);
-  if (rc == EMQX_OK && hipMemcpyAsync(sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s) != hipSuccess) rc = EMQX_EDEVICE;
-  if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;
-  h->inflight = false;
-  if (rc != EMQX_OK) return rc;
-  note_call(h, ms_since(t0));
-  return status_of(sum, summary_out);
-}
+  static int launch(emqx_window* h, const emqx_window_batch* b, uint8_t* p, const Layout& l, uint64_t* summary, hipStream_t s) {
+    return ::launch(h, b, p, l, summary, s);
+  }
+  static int status_of(const uint64_t* sum, uint64_t* summary_out) { return ::status_of(sum, summary_out); }
+};
 
 int run_batch(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out) {
   if (!h) return EMQX_EINVAL;
@@ -369,8 +228,8 @@ int run_batch(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out)
     uint64_t sum[WN_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (refused(b, m, sum)) return status_of(sum, summary_out);
   }
-  if (!offsets_ok(b, m)) return EMQX_EINVAL;
-  WN_TRY(hipSetDevice(h->device));
+  if (!offsets_ok(b->inbox_offsets, m)) return EMQX_EINVAL;
+  STAGE_TRY(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> g(h->mu);
   const uint64_t total = b->inbox_offsets[m];
@@ -393,24 +252,11 @@ int run_batch(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out)
     const int rc = reserve_locked(h, total, m);
     if (rc != EMQX_OK) return rc;
   }
-  // staging, every section 16-byte aligned
-  uint64_t at = 0;
-  auto place = [&at](uint64_t bytes) {
-    const uint64_t o = at;
-    at += (bytes + 15) & ~15ull;
-    return o;
-  };
-  const uint64_t o_sub = place(m * 4), o_off = place((m + 1) * 8), o_opt = place(total), o_tab = place(recs.size() * 32),
-                 o_ver = place(total), o_ids = place(total * 2), o_rec = place(m * 32), o_cnt = place(m * 16);
-  const uint64_t need = std::max<uint64_t>(at, 16);
-  if (h->stage_cap < need) {
-    drain(h);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    h->d_stage = nullptr;
-    h->stage_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_stage), need + need / 2) != hipSuccess) return EMQX_ENOMEM;
-    h->stage_cap = need + need / 2;
-  }
+  Stage st{16};
+  const uint64_t o_sub = st.place(m * 4), o_off = st.place((m + 1) * 8), o_opt = st.place(total), o_tab = st.place(recs.size() * 32),
+                 o_ver = st.place(total), o_ids = st.place(total * 2), o_rec = st.place(m * 32), o_cnt = st.place(m * 16);
+  const int src = stage_reserve(h, st.at, 16);
+  if (src != EMQX_OK) return src;
   hipStream_t s = h->stream;
   uint8_t* D = h->d_stage;
   d.inbox_subs = reinterpret_cast<const uint32_t*>(D + o_sub);
@@ -421,25 +267,19 @@ int run_batch(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out)
   d.pkt_ids = reinterpret_cast<uint16_t*>(D + o_ids);
   d.out_sessions = reinterpret_cast<emqx_window_session*>(D + o_rec);
   d.out_counts = reinterpret_cast<uint32_t*>(D + o_cnt);
-  auto up = [&](uint64_t o, const void* src, uint64_t bytes) {
-    return bytes == 0 || hipMemcpyAsync(D + o, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-  };
-  auto down = [&](void* dst, uint64_t o, uint64_t bytes) {
-    return bytes == 0 || hipMemcpyAsync(dst, D + o, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-  };
-  int rc = EMQX_OK;
-  if (h->inflight && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) rc = EMQX_EDEVICE;  // it may read the staging
-  bool ok = rc == EMQX_OK && up(o_sub, subs.data(), m * 4) && up(o_off, b->inbox_offsets, (m + 1) * 8) &&
-            up(o_opt, b->box_opts, total) && up(o_tab, recs.data(), m * 32);
-  if (!ok) rc = EMQX_EDEVICE;
-  uint64_t* d_sum = nullptr;
+  Copier cp = stage_copier(h);
+  cp.up(o_sub, subs.data(), m * 4);
+  cp.up(o_off, b->inbox_offsets, (m + 1) * 8);
+  cp.up(o_opt, b->box_opts, total);
+  cp.up(o_tab, recs.data(), m * 32);
   uint64_t sum[WN_S_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (rc == EMQX_OK) rc = enqueue(h, &d, nullptr, s, &d_sum);
-  if (rc == EMQX_OK && hipMemcpyAsync(sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s) != hipSuccess) rc = EMQX_EDEVICE;
+  int rc = cp.ok ? run_sync_locked<Policy>(h, &d, s, sum) : EMQX_EDEVICE;
   if (rc == EMQX_OK) {
-    ok = down(b->verdicts, o_ver, total) && down(b->pkt_ids, o_ids, total * 2) && down(b->out_sessions, o_rec, m * 32) &&
-         down(b->out_counts, o_cnt, m * 16);
-    if (!ok) rc = EMQX_EDEVICE;
+    cp.down(b->verdicts, o_ver, total);
+    cp.down(b->pkt_ids, o_ids, total * 2);
+    cp.down(b->out_sessions, o_rec, m * 32);
+    cp.down(b->out_counts, o_cnt, m * 16);
+    if (!cp.ok) rc = EMQX_EDEVICE;
   }
   if (hipStreamSynchronize(s) != hipSuccess) rc = EMQX_EDEVICE;
   h->inflight = false;
@@ -489,9 +329,7 @@ int window_stats_get(emqx_window* h, emqx_window_stats* out) {
   s.path = static_cast<uint64_t>(h->path);
   s.calls = h->calls;
   s.last_call_ms = h->last_call_ms;
-  const uint64_t nbytes = std::min<uint64_t>(out->size, sizeof(s));
-  s.size = nbytes;
-  std::memcpy(out, &s, nbytes);
+  stats_copy(out, s);
   return EMQX_OK;
 }
 
@@ -500,22 +338,22 @@ int window_stats_get(emqx_window* h, emqx_window_stats* out) {
 extern "C" {
 
 int emqx_window_create(int32_t device, emqx_window** out) {
-  return guarded([&] { return window_create(device, out); });
+  return guarded([&] { return stage_create(device, out); });
 }
 int emqx_window_destroy(emqx_window* h) {
-  return guarded([&] { return window_destroy(h); });
+  return guarded([&] { return stage_destroy(h); });
 }
 int emqx_window_reserve(emqx_window* h, uint64_t cap_in, uint64_t cap_boxes) {
-  return guarded([&] { return window_reserve(h, cap_in, cap_boxes); });
+  return guarded([&] { return reserve(h, cap_in, cap_boxes); });
 }
 int emqx_window_run_batch(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out) {
   return guarded([&] { return run_batch(h, b, summary_out); });
 }
 int emqx_window_run_batch_device(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out, void* stream) {
-  return guarded([&] { return run_batch_device(h, b, summary_out, stream); });
+  return guarded([&] { return run_batch_device<Policy>(h, b, summary_out, stream); });
 }
 int emqx_window_run_batch_device_async(emqx_window* h, const emqx_window_batch* b, uint64_t* summary, void* stream) {
-  return guarded([&] { return run_batch_device_async(h, b, summary, stream); });
+  return guarded([&] { return run_batch_device_async<Policy>(h, b, summary, stream); });
 }
 int emqx_window_run_host(emqx_window* h, const emqx_window_batch* b, uint64_t* summary_out) {
   return guarded([&] { return run_host(h, b, summary_out); });

@@ -311,6 +311,38 @@ def test_async_needs_the_scratch_reserved(T):
     assert h.stats()["scratch_bytes"] > 0 and h.stats()["cap_in"] == 10
 
 
+def test_misaligned_tables_are_refused(T, handle):
+    """One pointer at a time is off by half of what the device forms require of it (ring 16, heads 8,
+    sessions 16, out_counts 16, out_offsets 8): EMQX_EINVAL, nothing is enqueued, every byte stays."""
+    from emqx_amd import _lib
+    put = next(c for c in PUT_CASES if c.name == "head_wraps")
+    take = next(c for c in TAKE_CASES if c.name == "budget_ends_at_last")
+    n = put.ring.shape[0]
+    for field, by in (("ring", 8), ("heads", 4), ("sessions", 8)):
+        b = PutBatch(T, put)
+        assert getattr(b.args, field)
+        setattr(b.args, field, getattr(b.args, field) + by)
+        with pytest.raises(_lib.EngineError) as e:
+            handle.put_device(b.args)
+        assert e.value.code == -1
+        assert (b.ev.cpu().numpy() == S64).all() and (b.un.cpu().numpy().view(np.uint32) == S32).all()
+        assert back(b.ring, n * put.q, T.ENTRY, (n, put.q), "the ring").tobytes() == put.ring.tobytes()
+        assert back(b.heads, n, T.RING, (n,), "the headers").tobytes() == put.heads.tobytes()
+        assert back(b.sessions, 4 * put.sessions.size, C.SESSION, put.sessions.shape, "the table").tobytes() == put.sessions.tobytes()
+    n = take.ring.shape[0]
+    for field, by in (("ring", 8), ("heads", 4), ("sessions", 8), ("out_counts", 8), ("out_offsets", 4)):
+        b = TakeBatch(T, take)
+        assert getattr(b.args, field)
+        setattr(b.args, field, getattr(b.args, field) + by)
+        with pytest.raises(_lib.EngineError) as e:
+            handle.take_device(b.args)
+        assert e.value.code == -1
+        assert (b.off.cpu().numpy() == S64).all() and (b.cnt.cpu().numpy().view(np.uint32) == S32).all() and (b.status.cpu().numpy() == S8).all()
+        assert back(b.ring, n * take.q, T.ENTRY, (n, take.q), "the ring").tobytes() == take.ring.tobytes()
+        assert back(b.heads, n, T.RING, (n,), "the headers").tobytes() == take.heads.tobytes()
+        assert back(b.table, 4 * n, C.SESSION, (n,), "the table").tobytes() == take.sessions.tobytes()
+
+
 # ---- the cycle ----------------------------------------------------------------------------------
 
 def test_cycle_three_rounds_on_one_stream_with_no_host_read(T):

@@ -324,6 +324,31 @@ def test_async_needs_the_scratch_reserved(T):
     assert b.outputs(T).summary["sessions"] == b.m and h.stats()["calls"] == 1 and h.stats()["cap_boxes"] == b.cap_boxes
 
 
+def test_misaligned_tables_are_refused(T, handle):
+    """One pointer at a time is off by half of what the device forms require of it (ring 8, heads 64,
+    sessions 16, out_counts 16, out_offsets 8): EMQX_EINVAL, nothing is enqueued, every byte stays."""
+    from emqx_amd import _lib
+    put = next(c for c in PUT_CASES if c.name == "no_refs")
+    take = next(c for c in TAKE_CASES if c.name == "rotated_list")
+    for case, batch, call, fields in (
+            (put, PutBatch, handle.put_device, (("ring", 4), ("heads", 32), ("sessions", 8), ("out_counts", 8))),
+            (take, TakeBatch, handle.take_device, (("ring", 4), ("heads", 32), ("sessions", 8), ("out_counts", 8), ("out_offsets", 4)))):
+        for field, by in fields:
+            b = batch(T, case)
+            assert getattr(b.args, field)
+            setattr(b.args, field, getattr(b.args, field) + by)
+            with pytest.raises(_lib.EngineError) as e:
+                call(b.args)
+            assert e.value.code == -1
+            assert (b.cnt.cpu().numpy().view(np.uint32) == S32).all()
+            if batch is TakeBatch:
+                assert (b.off.cpu().numpy() == S64).all() and (b.status.cpu().numpy() == S8).all()
+            else:
+                assert (b.o_ver.cpu().numpy() == S8).all() and (b.ev.cpu().numpy() == S64).all()
+            sessions, ring, heads = b.result()
+            assert ring.tobytes() == case.ring.tobytes() and heads.tobytes() == case.heads.tobytes() and sessions.tobytes() == case.sessions.tobytes()
+
+
 # ---- the lattice: C x Qc x group width ------------------------------------------------------------
 
 def run_lattice(T, h, c, qc, g):
